@@ -481,6 +481,37 @@ def cpu_baseline(mode, n, m, seconds=12.0):
                       f"{threads} OpenMP threads (one env per thread iteration)"}
 
 
+DUMP_FIELDS = ("obs", "reward", "terminated", "truncated", "agent_active", "reset_happened", "actions", "episode_stats")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(b, path, rank):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the batch's output tensors (observations,
+    reward, terminated / truncated, agent mask, reset flag, the actions drawn in the kernel, the last ended episode's
+    return and length) -- as DIR/<name>.npy (float64 tensors as float64, everything else as float32), rank r > 0 as
+    DIR/<name>.rank<r>.npy.  Every tensor is [n_envs, ...]; when the whole set exceeds 64 MB a fixed seeded sample of the
+    envs is written instead, their indices beside it in env_index.npy.  Called right after the timed steps, before any
+    other launch touches the outputs; the env's draws are counter-based (Philox keyed by env id and step), so the same
+    arguments give the same files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    tensors = {k: getattr(b, k) for k in DUMP_FIELDS}
+    E = b.n_envs
+    out_size = {k: 8 if t.dtype == torch.float64 else 4 for k, t in tensors.items()}
+    per_env = sum(t[0].numel() * out_size[k] for k, t in tensors.items()) + 8
+    idx = None
+    if per_env * E > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(E, DUMP_LIMIT_BYTES // per_env, replace=False))
+        sel = torch.as_tensor(idx, device=b.device)
+        tensors = {k: t.index_select(0, sel) for k, t in tensors.items()}
+    arrays = {k: t.cpu().numpy().astype(np.float64 if out_size[k] == 8 else np.float32) for k, t in tensors.items()}
+    if idx is not None:
+        arrays["env_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def launch_check(args):
     """--launch-check: the multi-rank plumbing alone (no GPU): process group over ``--backend``, world
     size, per-rank env ranges, the metric all-reduce and the max-over-ranks time."""
@@ -517,7 +548,15 @@ def main():
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"])
     ap.add_argument("--physics", default="pyb", choices=["pyb", "dyn", "pyb_gnd", "pyb_drag", "pyb_dw", "pyb_gnd_drag_dw"],
                     help="Physics variant (BaseAviary.py:420-450); the headline is the reference default pyb")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else the line can hold: the end-of-rollout reduction "
+                         "and rollout metrics, per-kernel timing and the rooflines, the counter records, the "
+                         "terminal-observation, single-launch and near-herd legs, the host surfaces, the CPU baseline, "
+                         "and --policy / --train / --marl-vec.  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the outputs of the last timed step to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--policy", action="store_true",
                     help="also time a rollout driven by the on-device SB3 policy (model-v16-6 weights, CTDE only)")
@@ -543,6 +582,8 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the legs after the headline (terminal observations, host surfaces): counter passes")
     args = ap.parse_args()
+    if not args.full and (args.policy or args.train or args.marl_vec):
+        ap.error("--policy, --train and --marl-vec are legs of the full line: add --full")
 
     # --gpus N from a plain `python bench.py`: one child process per GPU, started before this
     # process touches the GPU (cattleherd.launch imports no torch)
@@ -582,9 +623,9 @@ def main():
 
     # end of a rollout (SURVEY §8(d) "host sync at the end"): device reduction of the per-env metric
     # rows, the RCCL all-reduce over xGMI (the rollout's only collective), one 64-byte copy to pinned
-    # memory and the stream sync
-    mbuf = torch.zeros(8, dtype=torch.float64, device=b.device)
-    mhost = torch.zeros(8, dtype=torch.float64).pin_memory()
+    # memory and the stream sync (measured by --full only)
+    mbuf = torch.zeros(8, dtype=torch.float64, device=b.device) if args.full else None
+    mhost = torch.zeros(8, dtype=torch.float64).pin_memory() if args.full else None
 
     def end_of_rollout():
         b.metrics_device(reset=True, out=mbuf)
@@ -616,7 +657,8 @@ def main():
     # the timed loop: K steps as whole graph replays of `chunk` steps (plus single launches for the rest)
     chunk = args.graph if args.graph > 0 and args.steps >= args.graph and spl == 1 else 0
     graph = b.capture_rollout(chunk) if chunk else None
-    end_of_rollout()   # warm: reduction kernel, pinned copy, first collective; zeroes the metric rows
+    if args.full:
+        end_of_rollout()   # warm: reduction kernel, pinned copy, first collective; zeroes the metric rows
     b.sync()
 
     def run(k):
@@ -646,8 +688,44 @@ def main():
     dt = time.perf_counter() - t0
     _, dt = D.reduce_rollout([0.0], dt, device=b.device)   # max over ranks
     b.sync()   # raises if a step kernel recorded a device error (hand-off timeout)
+    if args.dump_outputs:
+        dump_outputs(b, args.dump_outputs, rank)
+    from cattleherd import _lib as _L
+    multi_ran = spl > 1 and _L.lib().ch__multi_steps(b.handle) > 0   # (other geometries: one launch per step)
 
-    # the end of the rollout, after the timed steps: the device metric reduction of those K steps, the RCCL
+    # the headline: everything a plain run reports
+    out = None
+    if rank == 0:
+        value = E * world * args.steps / dt
+        out = {
+            "metric": "env-steps/sec (agent-steps/sec) at 4096 envs/GPU, 1/2/4/8 MI355X",
+            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1000.0, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.precision, "agent_steps_per_s": value * n,
+            "data": "synthetic: Philox4x32 random VEL actions in-kernel, spawn table from config/cattle_positions.yaml; "
+                    f"envs burnt in for {args.burn_in} untimed steps before the warmup (steady-state episode phases, "
+                    "auto-resets inside the timed steps at their long-run rate); headline without SB3 terminal "
+                    "observations (terminal_obs=False, the sync-free auto-reset path), the terminal-observation path in "
+                    "terminal_obs_leg (--full)",
+            "launch": (f"ch_step_n, {spl} steps per call: every workgroup steps its envs back to back in one "
+                       f"k_step2_multi launch (bit-identical to ch_step launches, tests/test_gpu_runtime.py)" if multi_ran else
+                       f"ch_step_n, {spl} steps per call, one launch per step (no multi-step kernel for this geometry)"
+                       if spl > 1 else
+                       f"HIP graph of {chunk} steps per replay" if graph is not None else "one host launch per step"),
+            "ranks": ranks,   # each rank's device index and PCI address (distinct, checked above)
+            "config": {"workload": desc, "envs_per_gpu": E, "num_drones": n, "num_cattle": m, "mode": mode,
+                       "physics": args.physics,
+                       "parallelism": f"env-sharded x{world} (no per-step collective)"},
+            "full": args.full,
+        }
+    if not args.full:
+        b.close()
+        D.shutdown()
+        if out is not None:
+            print(json.dumps(out), flush=True)
+        return
+
+    # --full from here on.  The end of the rollout, after the timed steps: the device metric reduction of those K steps, the RCCL
     # all-reduce over the ranks (the run's only collective; the path has no per-step exchange), the pinned copy
     torch.cuda.synchronize()
     te = time.perf_counter()
@@ -676,8 +754,6 @@ def main():
     achieved = bytes_step * E / (kern_us * 1e-6) / 1e9
     achieved_survey = survey_step * E / (kern_us * 1e-6) / 1e9
     default_cfg = E == WORKLOADS[args.workload][1] and args.physics == "pyb"
-    from cattleherd import _lib as _L
-    multi_ran = spl > 1 and _L.lib().ch__multi_steps(b.handle) > 0   # (other geometries: one launch per step)
     # the counter record of the kernel the headline ran (the multi-step kernel's per step, tools/counter_record.py --multi)
     rec_name = f"{args.workload}_{args.precision}" + ("_multi" if multi_ran else "")
     rec, rec_why = counter_record(rec_name) if default_cfg else ({}, "not a default workload")
@@ -726,29 +802,9 @@ def main():
                               "workgroup and the next launch"}
     wg = rec.get("wg_trace") or {}
 
-    out = None
     if rank == 0:
-        value = E * world * args.steps / dt
-        out = {
-            "metric": "env-steps/sec (agent-steps/sec) at 4096 envs/GPU, 1/2/4/8 MI355X",
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1000.0, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.precision, "agent_steps_per_s": value * n,
-            "data": "synthetic: Philox4x32 random VEL actions in-kernel, spawn table from config/cattle_positions.yaml; "
-                    f"envs burnt in for {args.burn_in} untimed steps before the warmup (steady-state episode phases, "
-                    "auto-resets inside the timed steps at their long-run rate); headline without SB3 terminal "
-                    "observations (terminal_obs=False, the sync-free auto-reset path), the terminal-observation path in "
-                    "terminal_obs_leg",
-            "launch": (f"ch_step_n, {spl} steps per call: every workgroup steps its envs back to back in one "
-                       f"k_step2_multi launch (bit-identical to ch_step launches, tests/test_gpu_runtime.py)" if multi_ran else
-                       f"ch_step_n, {spl} steps per call, one launch per step (no multi-step kernel for this geometry)"
-                       if spl > 1 else
-                       f"HIP graph of {chunk} steps per replay" if graph is not None else "one host launch per step"),
-            "ranks": ranks,   # each rank's device index and PCI address (distinct, checked above)
+        out.update({
             "rollout_end_us": rollout_end_us,
-            "config": {"workload": desc, "envs_per_gpu": E, "num_drones": n, "num_cattle": m, "mode": mode,
-                       "physics": args.physics,
-                       "parallelism": f"env-sharded x{world} (no per-step collective)"},
             # The kernel moves a few MB per launch and is bound by the latency of its dependent fp64 chains (the drone
             # wave's action -> PID -> 4 substeps -> bookkeeping), not by HBM or VALU throughput: the
             # HBM fraction is reported against 8 TB/s as the north_star asks, the chain/workgroup cycles beside it.
@@ -779,7 +835,7 @@ def main():
                                 # truncated envs keep stepping -- the steady state under random actions)
                                 "truncated_fraction": mv[5] / max(mv[0] * (n if mode == "marl" else 1), 1.0),
                                 "episode_ends_in_window": mv[1]},
-        }
+        })
         fr, fr_why = counter_record("flock_roofline")
         out["flock_roofline"] = fr.get("records") and {k: fr[k] for k in ("records", "flop_model", "peak_tflops", "note",
                                                                          "source") if k in fr} or fr_why

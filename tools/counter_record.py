@@ -53,7 +53,7 @@ def record(workload, dtype, raw, steps, timeout, multi=0):
     for tag, ctrs in PASSES.items():
         d = os.path.join(raw, f"{workload}_{dtype}_{tag}" + ("_multi" if multi else ""))
         tail = (["--counter-probe", str(multi)] if multi else
-                ["--steps", str(steps), "--warmup", "10", "--no-cpu-baseline", "--no-extras", "--steps-per-launch", "1"])
+                ["--full", "--steps", str(steps), "--warmup", "10", "--no-cpu-baseline", "--no-extras", "--steps-per-launch", "1"])
         cmd = ["timeout", "-s", "KILL", str(timeout), "rocprofv3", "--pmc", *ctrs.split(), "--output-format", "csv",
                "-d", d, "-o", "pmc", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload,
                "--precision", dtype, "--burn-in", "300", *tail]

@@ -16,7 +16,7 @@ for v in ${AB_VARIANTS:-_base DEFAULT}; do
   if [ -n "${AB_TRACE-ctde 4096 4 16}" ]; then
     CH_LIB_PATH=$PWD/$lib timeout -k 10 150 python -u tools/wg_trace.py ${AB_TRACE:-ctde 4096 4 16} >> $out 2>&1 || exit 1
   fi
-  CH_LIB_PATH=$PWD/$lib timeout -k 10 150 python -u bench.py ${AB_BENCH:---steps 1000 --warmup 100 --no-cpu-baseline} >> $out 2>&1 || exit 1
+  CH_LIB_PATH=$PWD/$lib timeout -k 10 150 python -u bench.py ${AB_BENCH:---full --steps 1000 --warmup 100 --no-cpu-baseline} >> $out 2>&1 || exit 1
 done
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ${PYTEST_ARGS:-} > gpurun_out/${AB_TAG:-ab}_pytest.log 2>&1

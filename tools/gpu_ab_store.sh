@@ -13,5 +13,5 @@ for v in "" ${AB_VARIANTS:-_nt _plain}; do
   [ -f $lib ] || continue
   echo "== variant '${v}'" >> $out
   CH_LIB_PATH=$PWD/$lib timeout -k 10 120 python -u tools/wg_trace.py >> $out 2>&1 || exit 1
-  CH_LIB_PATH=$PWD/$lib timeout -k 10 120 python -u bench.py --steps 1000 --warmup 100 --no-cpu-baseline >> $out 2>&1 || exit 1
+  CH_LIB_PATH=$PWD/$lib timeout -k 10 120 python -u bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline >> $out 2>&1 || exit 1
 done

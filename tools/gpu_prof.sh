@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-prof}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-WORK="python bench.py --steps ${STEPS:-60} --warmup 200 --no-cpu-baseline ${BENCH_ARGS:-}"
+WORK="python bench.py --full --steps ${STEPS:-60} --warmup 200 --no-cpu-baseline ${BENCH_ARGS:-}"
 i=0
 while read -r group; do
   [ -z "$group" ] && continue

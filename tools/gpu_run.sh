@@ -22,10 +22,10 @@ for s in ${STEPS:-tests smoke bench}; do
     tests) step pytest_gpu ${TEST_TIMEOUT:-1100} python -u -m pytest tests -m gpu -v -rf --timeout 300 --timeout-method thread ${PYTEST_ARGS:-}
            rc=$?; if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi ;;
     smoke) step smoke 300 python -u __graft_entry__.py smoke || exit 1 ;;
-    bench_driver) step bench_driver 400 python -u bench.py --steps 20 --warmup 5 || exit 1 ;;
-    bench) step bench 400 python -u bench.py ${BENCH_ARGS:-} || exit 1 ;;
+    bench_driver) step bench_driver 400 python -u bench.py --full --steps 20 --warmup 5 || exit 1 ;;
+    bench) step bench 400 python -u bench.py --full ${BENCH_ARGS:-} || exit 1 ;;
     counters) step counters 900 python -u tools/counter_record.py --workloads ${COUNTER_WORKLOADS:-c4 c5} --out $OUT/counters --raw $OUT/counters_raw || exit 1 ;;
-    rocprof) step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --steps 1000 --warmup 100 --no-cpu-baseline --no-extras ${BENCH_ARGS:-} || exit 1 ;;
+    rocprof) step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline --no-extras ${BENCH_ARGS:-} || exit 1 ;;
     flock) step flock 900 python -u tools/flock_roofline.py --out $OUT/counters || exit 1 ;;
     extra) step extra ${EXTRA_TIMEOUT:-600} bash -c "${EXTRA_CMD}" || exit 1 ;;
   esac

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 : > "$OUT/sweep.jsonl"
 run() {
   echo "=== $*" | tee -a "$OUT/steps.log"
-  timeout -k 10 240 python bench.py --no-cpu-baseline "$@" > "$OUT/last.log" 2>&1
+  timeout -k 10 240 python bench.py --full --no-cpu-baseline "$@" > "$OUT/last.log" 2>&1
   local rc=$?
   echo "=== rc=$rc" | tee -a "$OUT/steps.log"
   if [ $rc -ne 0 ]; then tail -20 "$OUT/last.log"; exit $rc; fi
