@@ -36,22 +36,13 @@ __constant__ static const Level kLevels[8] = {
     {0.8, 0.3, 15, 0.2, 50, 0.0, 0.0, 4, 12, 80, 0.0, 0.0, -0.0, 1, 1, 0.0, 600},
 };
 
-// Heavy libm entry points go through one out-of-line copy each (CH_NOINLINE_MATH) instead of being
-// inlined at every call site: the fused step kernel is otherwise ~11k instructions and thrashes the
-// shared instruction cache.
-#ifdef CH_NOINLINE_MATH
-#define CH_MATH_ATTR __device__ __noinline__
-#else
-#define CH_MATH_ATTR __device__ __forceinline__
-#endif
-template <class R> CH_MATH_ATTR R m_atan2(R y, R x) { return atan2(y, x); }
-template <class R> CH_MATH_ATTR R m_asin(R x) { return asin(x); }
-template <class R> CH_MATH_ATTR R m_exp(R x) { return exp(x); }
-template <class R> CH_MATH_ATTR R m_cos(R x) { return cos(x); }
-template <class R> CH_MATH_ATTR R m_sin(R x) { return sin(x); }
-template <class R> CH_MATH_ATTR R m_pow(R x, R y) { return pow(x, y); }
+// The libm entry points the kernels use, inlined at every call site.  (One out-of-line copy each, to shrink the
+// fused step kernel's instruction footprint, measured slower: DESIGN_HISTORY.md A.6.)
+template <class R> __device__ __forceinline__ R m_atan2(R y, R x) { return atan2(y, x); }
+template <class R> __device__ __forceinline__ R m_asin(R x) { return asin(x); }
+template <class R> __device__ __forceinline__ R m_exp(R x) { return exp(x); }
 // sin and cos of one argument share the range reduction
-template <class R> CH_MATH_ATTR void m_sincos(R x, R* s, R* c) {
+template <class R> __device__ __forceinline__ void m_sincos(R x, R* s, R* c) {
     if constexpr (sizeof(R) == 8) sincos(x, s, c);
     else sincosf(x, s, c);
 }
@@ -680,11 +671,7 @@ __device__ __forceinline__ void sincos_pi(double x, double* s, double* c) {
 template <class R> __device__ __forceinline__ R bump(R z) {
     if (z < R(0)) return R(0);
     if (z < R(kH)) return R(1);
-#ifdef CH_OCML_COS
-    if (z <= R(1)) return (R(1) + m_cos(divc(R(kPi) * (z - R(kH)), R(1) - R(kH)))) / R(2);
-#else
     if (z <= R(1)) return (R(1) + cos_0pi(divc(R(kPi) * (z - R(kH)), R(1) - R(kH)))) / R(2);
-#endif
     return R(0);
 }
 template <class R> __device__ __forceinline__ R sigma_1(R z) { return z / sqrt(R(1) + z * z); }

@@ -80,7 +80,7 @@ struct StepParams {
 };
 
 // device error word bits (ch_api.cpp reports them as CH_ERR_DEVICE)
-constexpr int CH_DEVERR_HANDOFF = 1;       // a v2 LDS hand-off wait ran out of spins (ch_step.hip lds_wait)
+constexpr int CH_DEVERR_HANDOFF = 1;       // a v2 LDS hand-off wait ran out of spins (ch_step_body.h lds_wait)
 // diagnostics phase_mask bits beyond 1/2/4/8 (skip drones / flock / task / obs)
 constexpr int CH_PHASE_FORCE_TIMEOUT = 64; // test only: the drone wave waits for a hand-off that never comes
 
@@ -93,7 +93,7 @@ struct Level {
     int required_tally;
 };
 
-// LDS carve of one v2 step workgroup (ch_step.hip); identical on host (size) and device (offsets).
+// LDS carve of one v2 step workgroup (ch_step_body.h); identical on host (size) and device (offsets).
 #ifndef CH_V2_MAX_BLOCK
 #define CH_V2_MAX_BLOCK 768   // v2 workgroup size bound: 12 waves, 3 per SIMD (shared-table kernels)
 #endif

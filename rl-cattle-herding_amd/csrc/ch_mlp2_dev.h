@@ -21,7 +21,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // error of a small |v| is larger -- the tests hold the forward's outputs, i.e. absolute errors of the hidden units
 // summed through the next layer, to 1e-5 and 2e-5), about 8 instructions instead of ocml's tanhf.  A 64-row tile
 // applies it to 64 values per lane and layer, which made the epilogues as long as the matrix loops.
-// CH_OCML_TANH: ocml's tanhf.
 constexpr float kTanhScale = 2.8853900817779268f;   // 2 log2(e): 2^(kTanhScale v) = e^(2v)
 // tanh from s = kTanhScale v (the hidden epilogue folds its bias into the fma that forms s): 5 instructions, two of
 // them transcendental, with the bias add
@@ -29,11 +28,7 @@ __device__ __forceinline__ float tanh_fast_scaled(float s) {
     return fmaf(-2.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s) + 1.0f), 1.0f);
 }
 __device__ __forceinline__ float tanh_fast(float v) {
-#ifdef CH_OCML_TANH
-    return tanhf(v);
-#else
     return tanh_fast_scaled(v * kTanhScale);
-#endif
 }
 
 __device__ __forceinline__ float act_fn(float v, int act) {
@@ -279,11 +274,7 @@ __device__ __forceinline__ void mlp2_epi_hidden(const f32x4 (&acc)[RT][TW], cons
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v;
-#ifdef CH_OCML_TANH
-                if constexpr (ACT == CH_ACT_TANH) v = tanhf(acc[t][j][r] + bcol[j]);
-#else
                 if constexpr (ACT == CH_ACT_TANH) v = tanh_fast_scaled(fmaf(acc[t][j][r], kTanhScale, bs));
-#endif
                 else if constexpr (ACT == CH_ACT_RELU) { v = acc[t][j][r] + bcol[j]; v = v > 0.0f ? v : 0.0f; }
                 else v = acc[t][j][r] + bcol[j];
                 out[(16 * t + (lane >> 4) * 4 + r) * ldh + col] = v;

@@ -1,11 +1,10 @@
 // ch_step_multi.hip — ch_step_n's kernel: n consecutive steps of a handle in one launch (k_step2_multi).
 //
-// The step is ch_step.hip's step2_body (included here for it alone).  This translation unit is compiled with machine
-// LICM off (cattleherd/_build.py): with it, the step loop hoisted the body's loop-invariant values (LDS addresses,
-// constants) to the loop preheader and held them across the whole step, and configs[3]'s instantiation spilled 80-145
-// VGPRs; without it the body keeps k_step2's register allocation (173 VGPRs, no scratch).
-#define CH_STEP_BODY_ONLY
-#include "ch_step.hip"
+// The step is step2_body (ch_step_body.h), the same function k_step2 runs.  This translation unit is compiled with
+// machine LICM off (cattleherd/_build.py): with it, the step loop hoisted the body's loop-invariant values (LDS
+// addresses, constants) to the loop preheader and held them across the whole step, and configs[3]'s instantiation
+// spilled 80-145 VGPRs; without it the body keeps k_step2's register allocation (173 VGPRs, no scratch).
+#include "ch_step_body.h"
 
 namespace ch {
 
