@@ -3,6 +3,7 @@
 // Host side: validates the configuration the way the reference's constructors do, owns the SoA
 // state in HBM, and launches the kernels in ch_kernels.hip.  No host<->device traffic on the
 // ch_step path: actions, observations, rewards and flags stay in caller-owned device buffers.
+// The policy forwards and the rollout collections are in ch_api_policy.cpp; both share ch_handle.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,102 +15,13 @@
 #include <string>
 #include <vector>
 
-#include "ch_internal.h"
+#include "ch_handle.h"
 #include "ch_spawn_table.inc"
 
 using namespace ch;
 
-struct ch_handle {
-    ch_config cfg{};
-    int64_t E = 0;
-    int device = 0;
-    int NC = 0, M = 0, rows = 0, K = 0, team = 0;
-    int start_level = 0;
-    double episode_len = 0;
-    size_t rsize = 8;
-    void* drone = nullptr;
-    // Euler angles of each drone's stored quaternion, written by the v2 step at the end of every
-    // step (it needs them for the observation anyway) and read by the next one instead of
-    // recomputing atan2/asin/atan2; any other writer of the state clears rpy_valid.
-    void* rpy = nullptr;
-    uint8_t* stale = nullptr;   // device [2][E]: StepParams::stale (Euler cache stale, obs bytes unknown, per env)
-    unsigned long long* obs_tag = nullptr;   // device [E]: StepParams::obs_tag (the buffer holding env e's constant obs bytes)
-    void* cattle = nullptr;
-    void* phys = nullptr;   // [kPhysComps][E][NC]: last_clipped_action, DYN rpy_rates
-    void* envr = nullptr;
-    // f32 mode only: the f64 copies of the positions and prev_cent_dists the step integrates and measures
-    // centroids on (StepParams::pos64 / cpos64 / prev64); the f32 arrays above keep their rounded values
-    double* pos64 = nullptr;    // [3][E][NC]
-    double* cpos64 = nullptr;   // [2][E][M]
-    double* prev64 = nullptr;   // [E]
-    int* envi = nullptr;
-    double* metrics = nullptr;
-    double* spawn = nullptr;
-    int n_scen = 0, n_cows = 0;
-    double* debug = nullptr;
-    int phase_mask = 0;
-    // The obs buffer whose constant-zero bytes (rows >= NUM_DRONES, the action-buffer block, padding)
-    // are known to hold zeros: the last one a full-block writer (v1 step, full ch_reset, v2 step with
-    // obs_full) wrote.  The v2 step then stores only the entries that change.
-    const float* obs_zero_ptr = nullptr;
-    // v2 step kernel (ch_step.hip): envs per workgroup, block size, dynamic LDS, cow-pair list
-    int kernel = 2;
-    long long* tstamp = nullptr;
-    int G = 1, block = 64, P = 0;
-    bool pw = false;   // v2 with per-wave env tables (herds of kPwMinCattle cows and more)
-    bool sep = false;  // v2 shared tables with the shepherd terms in their own LDS region
-    size_t lds = 0;
-    uint16_t* pairs = nullptr;
-    int* errw = nullptr;        // device error word (CH_DEVERR_* bits), sticky
-    double* evald = nullptr;    // [E][NC] evaluation distances (cfg.eval_metrics)
-    int* rdn = nullptr;         // ch_reset_with: device copies of the injected draws
-    double* rdv = nullptr;
-    double* mdev = nullptr;     // device [CH_METRIC_COUNT + 1]: reduced metrics + error word
-    double* mhost = nullptr;    // pinned host copy of mdev
-    // ch_rollout_collect's deferred-bootstrap queue (allocated on first use): terminal observations, their rewards
-    // rows, the count, the values
-    float* tv_obs = nullptr;
-    long long* tv_row = nullptr;
-    int* tv_count = nullptr;
-    float* tv_val = nullptr;
-    size_t tv_obs_n = 0, tv_val_n = 0;
-    // ch_rollout_collect's path (diagnostics / tests, ch__set_rollout_path): bit 0 copy every step's observation into
-    // the buffer instead of stepping into its slots, bit 1 the stand-alone store kernel instead of the forward epilogues,
-    // bit 2 the actor forward fused into the step kernel (k_step2_actor, where the geometry takes it), bit 3 never fused
-    int rollout_path = 0;
-    long long fused_steps = 0;   // fused steps launched by ch_rollout_collect (ch__rollout_fused_steps)
-    long long multi_steps = 0;   // steps ch_step_n ran inside k_step2_multi (ch__multi_steps)
-    void* d_params = nullptr;    // k_step2_multi's parameters (device copy, ch_step_n)
-    std::vector<unsigned char> params_host;   // what d_params holds (uploaded again only when the parameters change)
-    // ch_outputs_to_host's device staging of the envs that auto-reset (allocated on first use): count, indices,
-    // episode statistics, terminal observation blocks; and the pinned host copy of the count
-    long long* st_count = nullptr;
-    long long* st_env = nullptr;
-    double* st_stats = nullptr;
-    float* st_obs = nullptr;
-    long long* st_count_host = nullptr;
-    // how many ended envs ch_outputs_to_host copies before it knows the count: twice the larger of the last count and
-    // its running mean, plus 8 (a step where more end costs one more copy and stream sync)
-    double ended_mean = 8.0;
-    int64_t ended_last = 8;
-    // the device error word was reported to the caller (device_status) since it was last cleared
-    bool err_seen = false;
-    std::string err;
-};
-
-static thread_local std::string g_create_err;
-
-static int fail(ch_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_err = msg;
-    return code;
-}
-
-#define HIP_TRY(h, expr)                                                                           \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail((h), CH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
+// the message of a failure without a handle (ch_handle.h)
+thread_local std::string g_create_err;
 
 // episode_length per curriculum level (curriculum_learning.py:24-182)
 static const double kEpisodeLen[8] = {40, 40, 40, 40, 80, 40, 80, 80};
@@ -270,11 +182,14 @@ static void free_all(ch_handle* h) {
                     h->d_params};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)h->tv_obs, (void*)h->tv_row, (void*)h->tv_count, (void*)h->tv_val, (void*)h->st_count,
-                    (void*)h->st_env, (void*)h->st_stats, (void*)h->st_obs})
-        if (p) (void)hipFree(p);
     if (h->mhost) (void)hipHostFree(h->mhost);
-    if (h->st_count_host) (void)hipHostFree(h->st_count_host);
+    const ch_rollout_state& ro = h->ro;   // the rollout's queue
+    for (void* p : {(void*)ro.tv_obs, (void*)ro.tv_row, (void*)ro.tv_count, (void*)ro.tv_val})
+        if (p) (void)hipFree(p);
+    const ch_staging& sg = h->st;         // ch_outputs_to_host's staging
+    for (void* p : {(void*)sg.count, (void*)sg.env, (void*)sg.stats, (void*)sg.obs})
+        if (p) (void)hipFree(p);
+    if (sg.count_host) (void)hipHostFree(sg.count_host);
 }
 
 // the sticky device error word as a status (call after the stream has drained)
@@ -347,7 +262,7 @@ int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** ou
         const char* v = getenv("CH_ROLLOUT_COPY");
         const char* k = getenv("CH_ROLLOUT_STORE_KERNEL");
         const char* f = getenv("CH_FUSED_ACTOR");
-        h->rollout_path = ((v && v[0] == '1') ? 1 : 0) | ((k && k[0] == '1') ? 2 : 0) | ((f && f[0] == '1') ? 4 : 0);
+        h->ro.path = ((v && v[0] == '1') ? 1 : 0) | ((k && k[0] == '1') ? 2 : 0) | ((f && f[0] == '1') ? 4 : 0);
     }
 
     auto cleanup = [&](int code) { free_all(h); std::string m = h->err; delete h; g_create_err = m; return code; };
@@ -606,7 +521,9 @@ int ch_reset_with(ch_handle* h, const uint8_t* mask_dev, const int32_t* num_dron
     return mask_dev ? CH_OK : clear_error_word(h, st, "ch_reset_with");   // as ch_reset
 }
 
-extern "C++" template <class P>
+}  // extern "C"
+
+template <class P>
 static void fill_step(const ch_handle* h, const ch_step_io* io, P& p) {
     p.actions = io->actions; p.actions_out = io->actions_out; p.obs = io->obs; p.reward = io->reward;
     p.term = io->terminated; p.trunc = io->truncated; p.terminal_obs = io->terminal_obs;
@@ -615,42 +532,42 @@ static void fill_step(const ch_handle* h, const ch_step_io* io, P& p) {
     p.obs_full = io->obs != h->obs_zero_ptr;
 }
 
-// ch_rollout_collect's fused step (launch_step_v2_actor): the step of `io` with the actor forward `fa` on the
-// observations it writes (fa.x == io->obs) and the sampling epilogue `ro`.  launch = false: hipSuccess iff the handle
-// and the net fit the fused kernel (nothing launched).
-static hipError_t step_actor(ch_handle* h, const ch_step_io* io, hipStream_t st, const MlpArgs& fa, const RolloutArgs& ro,
-                             bool launch) {
+// ch_rollout_collect's fused step (ch_handle.h)
+hipError_t step_actor(ch_handle* h, const ch_step_io* io, hipStream_t st, const MlpArgs& fa, const RolloutArgs& ro,
+                      bool launch) {
     if (h->kernel != 2 || h->rsize != sizeof(double) || h->phase_mask) return hipErrorNotSupported;
     StepParams<double> p = params<double>(h);
     fill_step(h, io, p);
     const hipError_t e = launch_step_v2_actor(p, h->block, h->lds, st, fa, ro, launch);
-    if (e == hipSuccess && launch) { h->obs_zero_ptr = io->obs; ++h->fused_steps; }
+    if (e == hipSuccess && launch) { h->obs_zero_ptr = io->obs; ++h->ro.fused_steps; }
     return e;
 }
 
-int ch_step(ch_handle* h, const ch_step_io* io, void* stream) {
-    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_step: NULL handle");
-    if (!io) return fail(h, CH_ERR_INVALID, "ch_step: io is NULL");
+// what ch_step and ch_step_n ask of their io
+static int validate_step_io(ch_handle* h, const ch_step_io* io, const char* who) {
+    auto bad = [&](const char* what) { return fail(h, CH_ERR_INVALID, std::string(who) + ": " + what); };
+    if (!io) return bad("io is NULL");
     if (!io->obs || !io->reward || !io->terminated || !io->truncated)
-        return fail(h, CH_ERR_INVALID, "ch_step: obs, reward, terminated and truncated are required");
+        return bad("obs, reward, terminated and truncated are required");
     if (!(io->flags & CH_STEP_RANDOM_ACTIONS) && !io->actions)
-        return fail(h, CH_ERR_INVALID, "ch_step: actions is NULL (and CH_STEP_RANDOM_ACTIONS not set)");
-    if (io->actions && (reinterpret_cast<uintptr_t>(io->actions) & 15))
-        return fail(h, CH_ERR_INVALID, "ch_step: actions must be 16-byte aligned");
+        return bad("actions is NULL (and CH_STEP_RANDOM_ACTIONS not set)");
+    if (io->actions && (reinterpret_cast<uintptr_t>(io->actions) & 15)) return bad("actions must be 16-byte aligned");
     if ((reinterpret_cast<uintptr_t>(io->obs) & 15) ||
         (io->terminal_obs && (reinterpret_cast<uintptr_t>(io->terminal_obs) & 15)))
-        return fail(h, CH_ERR_INVALID, "ch_step: obs buffers must be 16-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
+        return bad("obs buffers must be 16-byte aligned");
+    return CH_OK;
+}
+
+// one step of a validated io on the handle's device (ch_step; ch_step_n's plain steps)
+static int step_once(ch_handle* h, const ch_step_io* io, hipStream_t st) {
     hipError_t e;
-    auto fill = [&](auto& p) { fill_step(h, io, p); };
     if (h->rsize == sizeof(double)) {
         StepParams<double> p = params<double>(h);
-        fill(p);
+        fill_step(h, io, p);
         e = h->kernel == 2 ? launch_step_v2(p, h->block, h->lds, st) : launch_step(p, h->team, st);
     } else {
         StepParams<float> p = params<float>(h);
-        fill(p);
+        fill_step(h, io, p);
         e = h->kernel == 2 ? launch_step_v2(p, h->block, h->lds, st) : launch_step(p, h->team, st);
     }
     if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_step launch: ") + hipGetErrorString(e));
@@ -663,34 +580,35 @@ int ch_step(ch_handle* h, const ch_step_io* io, void* stream) {
     return CH_OK;
 }
 
+extern "C" {
+
+int ch_step(ch_handle* h, const ch_step_io* io, void* stream) {
+    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_step: NULL handle");
+    if (int rc = validate_step_io(h, io, "ch_step")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return step_once(h, io, (hipStream_t)stream);
+}
+
 int ch_step_n(ch_handle* h, const ch_step_io* io, int32_t n_steps, void* stream) {
     if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_step_n: NULL handle");
     if (n_steps < 1) return fail(h, CH_ERR_INVALID, "ch_step_n: n_steps must be >= 1");
-    if (!io) return fail(h, CH_ERR_INVALID, "ch_step_n: io is NULL");
-    // the same validation as ch_step
-    if (!io->obs || !io->reward || !io->terminated || !io->truncated)
-        return fail(h, CH_ERR_INVALID, "ch_step_n: obs, reward, terminated and truncated are required");
-    if (!(io->flags & CH_STEP_RANDOM_ACTIONS) && !io->actions)
-        return fail(h, CH_ERR_INVALID, "ch_step_n: actions is NULL (and CH_STEP_RANDOM_ACTIONS not set)");
-    if ((io->actions && (reinterpret_cast<uintptr_t>(io->actions) & 15)) || (reinterpret_cast<uintptr_t>(io->obs) & 15) ||
-        (io->terminal_obs && (reinterpret_cast<uintptr_t>(io->terminal_obs) & 15)))
-        return fail(h, CH_ERR_INVALID, "ch_step_n: actions and obs buffers must be 16-byte aligned");
+    int done = 0, rc = validate_step_io(h, io, "ch_step_n");
+    if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    int done = 0, rc = CH_OK;
     // under stream capture: n_steps plain launches (a captured multi-step launch would read the handle's parameter copy
     // as a later call left it, and the upload's host source would not outlive the call)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
     if (cap != hipStreamCaptureStatusNone) {
         for (int k = 0; k < n_steps; ++k)
-            if ((rc = ch_step(h, io, stream)) != CH_OK) return rc;
+            if ((rc = step_once(h, io, st)) != CH_OK) return rc;
         return CH_OK;
     }
     // a buffer whose constant observation bytes are not known to be in place gets one plain step first (it writes
     // them); every step of the multi-step kernel then finds them there
     if (io->obs != h->obs_zero_ptr || h->kernel != 2 || h->phase_mask) {
-        if ((rc = ch_step(h, io, stream)) != CH_OK) return rc;
+        if ((rc = step_once(h, io, st)) != CH_OK) return rc;
         done = 1;
     }
     if (done == n_steps) return CH_OK;
@@ -724,7 +642,7 @@ int ch_step_n(ch_handle* h, const ch_step_io* io, int32_t n_steps, void* stream)
     if (e != hipErrorNotSupported) return fail(h, CH_ERR_DEVICE, std::string("ch_step_n launch: ") + hipGetErrorString(e));
     (void)hipGetLastError();
     for (int k = 0; k < rest; ++k)   // other geometries: one launch per step
-        if ((rc = ch_step(h, io, stream)) != CH_OK) return rc;
+        if ((rc = step_once(h, io, st)) != CH_OK) return rc;
     return CH_OK;
 }
 
@@ -867,463 +785,9 @@ int ch__obs_invalidate(ch_handle* h, void* stream) {
     return CH_OK;
 }
 
-// diagnostics: k_mlp2 writes wave 0's phase clocks of every workgroup to dev[blockIdx][16] (NULL: off); the fused
-// step + actor kernel (k_step2_actor) writes its forward's clocks and wall-clock slots 13-15 to rows [grid, 2 grid),
-// so a buffer for a collection on the fused path holds 2 x 16 x (E / 16) entries (tools/fused_probe.py trace)
-extern "C" int ch__set_mlp_tstamp(long long* dev) {
-    g_mlp_tstamp = dev;
-    return CH_OK;
-}
-
-/* Internal (tests / diagnostics): ch_rollout_collect's path, bit 0 copy each step's observation into the buffer
- * (CH_ROLLOUT_COPY=1), bit 1 the stand-alone store kernel instead of the forward epilogues (CH_ROLLOUT_STORE_KERNEL=1),
- * bit 2 the actor forward fused into the step (CH_FUSED_ACTOR=1), bit 3 never fused. */
-int ch__set_rollout_path(ch_handle* h, int32_t bits) {
-    if (!h || bits < 0 || bits > 15) return CH_ERR_INVALID;
-    h->rollout_path = bits;
-    return CH_OK;
-}
-
-/* Internal: the handle's current rollout path bits (ch__set_rollout_path), or -1 for a null handle. */
-int ch__get_rollout_path(const ch_handle* h) { return h ? h->rollout_path : -1; }
-
-/* Internal (tests): steps ch_rollout_collect has launched as the fused step + actor kernel on this handle. */
-int64_t ch__rollout_fused_steps(const ch_handle* h) { return h ? (int64_t)h->fused_steps : -1; }
-
 int ch__set_phase_mask(ch_handle* h, int32_t mask) {
     if (!h) return CH_ERR_INVALID;
     h->phase_mask = mask;
-    return CH_OK;
-}
-
-static int mlp_args(const ch_mlp* net, const float* x, int64_t rows, float* y, MlpArgs& a, std::string& err) {
-    if (!net || !x || !y) { err = "NULL argument"; return CH_ERR_INVALID; }
-    if (net->n_layers < 1 || net->n_layers > 4) { err = "n_layers must be 1..4"; return CH_ERR_INVALID; }
-    if (rows < 0) { err = "rows < 0"; return CH_ERR_INVALID; }
-    std::memset(&a, 0, sizeof(a));
-    a.layers = net->n_layers;
-    for (int i = 0; i <= net->n_layers; ++i) {
-        a.dims[i] = net->dims[i];
-        if (net->dims[i] < 1 || (i > 0 && net->dims[i] > 256)) { err = "layer widths must be 1..256"; return CH_ERR_UNSUPPORTED; }
-    }
-    for (int i = 0; i < net->n_layers; ++i) {
-        if (!net->weight[i]) { err = "NULL weight"; return CH_ERR_INVALID; }
-        a.w[i] = net->weight[i]; a.b[i] = net->bias[i];
-    }
-    if (net->hidden_act < CH_ACT_NONE || net->hidden_act > CH_ACT_RELU) { err = "unknown activation"; return CH_ERR_INVALID; }
-    a.hidden_act = net->hidden_act; a.clip = net->clip != 0; a.lo = net->lo; a.hi = net->hi;
-    a.x = x; a.rows = rows; a.y = y; a.rows_per_env = 1;
-    a.kcap = net->dims[0];
-    // float4 weight loads need 16-B aligned rows of a multiple of 8 floats (k_mlp2 reads 8 per lane), inputs 4
-    for (int i = 0; i < net->n_layers; ++i)
-        if (net->dims[i] % 8 == 0 && (reinterpret_cast<uintptr_t>(net->weight[i]) & 15) == 0) a.vec_w |= 1 << i;
-    if (net->dims[0] % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) a.vec_w |= 1 << 7;
-    // block-diagonal layers the kernel can skip by whole K-pair groups (ch_mlp.split_*); others run dense
-    for (int i = 1; i < net->n_layers; ++i) {
-        const int so = net->split_out[i], si = net->split_in[i];
-        if (so > 0 && so < net->dims[i + 1] && so % 32 == 0 && si > 0 && si < net->dims[i] && si % 128 == 0) {
-            a.split_out[i] = so; a.split_in[i] = si;
-        }
-    }
-    if (net->packed) {
-        if (reinterpret_cast<uintptr_t>(net->packed) & 15) { err = "packed weights must be 16-byte aligned"; return CH_ERR_INVALID; }
-        a.packed = net->packed;
-        mlp_packed_floats(a.layers, a.dims, a.pk_off, a.pk_pairs);
-    }
-    return CH_OK;
-}
-
-int64_t ch_mlp_packed_size(const ch_mlp* net) {
-    if (!net || net->n_layers < 1 || net->n_layers > 4) return -1;
-    for (int i = 0; i <= net->n_layers; ++i)
-        if (net->dims[i] < 1 || (i > 0 && net->dims[i] > 256)) return -1;
-    return mlp_packed_floats(net->n_layers, net->dims, nullptr, nullptr);
-}
-
-int ch_mlp_pack(const ch_mlp* net, float* dst, void* stream) {
-    MlpArgs a;
-    std::string err;
-    float one = 0.0f;
-    const int rc = mlp_args(net, &one, 0, &one, a, err);
-    if (rc) return fail(nullptr, rc, "ch_mlp_pack: " + err);
-    if (!dst || (reinterpret_cast<uintptr_t>(dst) & 15)) return fail(nullptr, CH_ERR_INVALID, "ch_mlp_pack: dst NULL or not 16-byte aligned");
-    const hipError_t e = launch_mlp_pack(a, dst, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, std::string("ch_mlp_pack launch: ") + hipGetErrorString(e));
-    return CH_OK;
-}
-
-int ch_mlp_forward(const ch_mlp* net, const float* x, int64_t rows, float* y, void* stream) {
-    MlpArgs a;
-    std::string err;
-    const int rc = mlp_args(net, x, rows, y, a, err);
-    if (rc) return fail(nullptr, rc, "ch_mlp_forward: " + err);
-    const hipError_t e = launch_mlp(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, std::string("ch_mlp_forward launch: ") + hipGetErrorString(e));
-    return CH_OK;
-}
-
-int ch_mlp_forward_masked(const ch_mlp* net, const float* x, int64_t rows, const uint8_t* row_mask, float* y,
-                          void* stream) {
-    MlpArgs a;
-    std::string err;
-    const int rc = mlp_args(net, x, rows, y, a, err);
-    if (rc) return fail(nullptr, rc, "ch_mlp_forward_masked: " + err);
-    if (!row_mask) return fail(nullptr, CH_ERR_INVALID, "ch_mlp_forward_masked: NULL row mask");
-    a.row_mask = row_mask;
-    const hipError_t e = launch_mlp(a, (hipStream_t)stream);
-    if (e != hipSuccess)
-        return fail(nullptr, CH_ERR_DEVICE, std::string("ch_mlp_forward_masked launch: ") + hipGetErrorString(e));
-    return CH_OK;
-}
-
-// the forward of `net` on a handle's observation buffer: one row per env (CTDE) or agent (MARL), live widths from
-// NUM_DRONES (envi row 0)
-static int policy_args(ch_handle* h, const ch_mlp* net, const float* obs, float* y, MlpArgs& a, const char* who) {
-    const bool marl = h->cfg.mode == CH_MODE_MARL;
-    const int64_t rows = marl ? h->E * h->NC : h->E;
-    const int want = marl ? 86 : h->rows * 86;
-    if (net && net->dims[0] != want)
-        return fail(h, CH_ERR_INVALID, std::string(who) + ": dims[0] must be " + std::to_string(want) + " for this handle");
-    std::string err;
-    const int rc = mlp_args(net, obs, rows, y, a, err);
-    if (rc) return fail(h, rc, std::string(who) + ": " + err);
-    a.env_n = h->envi;   // envi row 0: NUM_DRONES of the episode each env is in
-    a.rows_per_env = marl ? h->NC : 1;
-    a.k_unit = 86;
-    a.kcap = std::min(a.dims[0], marl ? 86 : h->NC * 86);   // NUM_DRONES <= the constructor's drones
-    return CH_OK;
-}
-
-int ch_policy_forward(ch_handle* h, const ch_mlp* net, const float* obs, float* y, void* stream) {
-    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_policy_forward: NULL handle");
-    MlpArgs a;
-    const int rc = policy_args(h, net, obs, y, a, "ch_policy_forward");
-    if (rc) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const hipError_t e = launch_mlp(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_policy_forward launch: ") + hipGetErrorString(e));
-    return CH_OK;
-}
-
-static int rollout_args(ch_handle* h, const ch_rollout* rb, RolloutArgs& a, const char* who) {
-    if (!h) return fail(nullptr, CH_ERR_INVALID, std::string(who) + ": NULL handle");
-    if (!rb) return fail(h, CH_ERR_INVALID, std::string(who) + ": NULL rollout buffer");
-    if (h->cfg.mode != CH_MODE_CTDE)
-        return fail(h, CH_ERR_UNSUPPORTED, std::string(who) + ": the SB3 rollout buffer is for CTDE handles");
-    // the env reads a (num_drones, 4) action per env (ch_step: float4 [e * num_drones + k]), so the policy must
-    // produce at least num_drones * 4 outputs (SB3: Box((NUM_DRONES, 4)) or the reference's (12, 4))
-    if (rb->n_steps < 1 || rb->act_dim < h->NC * 4 || rb->act_dim > 256)
-        return fail(h, CH_ERR_INVALID, std::string(who) + ": n_steps >= 1 and num_drones * 4 = " +
-                                           std::to_string(h->NC * 4) + " <= act_dim <= 256 required");
-    std::memset(&a, 0, sizeof(a));
-    a.T = rb->n_steps; a.rows = h->E; a.obs_dim = h->rows * 86; a.act_dim = rb->act_dim;
-    a.env_act_dim = h->NC * 4;
-    a.mean_ld = rb->act_dim; a.value_ld = 1; a.tv_ld = 1; a.post_prev = 0;
-    a.obs = rb->obs; a.actions = rb->actions; a.rewards = rb->rewards; a.episode_starts = rb->episode_starts;
-    a.values = rb->values; a.log_probs = rb->log_probs; a.advantages = rb->advantages; a.returns = rb->returns;
-    a.last_episode_starts = rb->last_episode_starts;
-    return CH_OK;
-}
-
-int ch_rollout_store(ch_handle* h, const ch_rollout* rb, int32_t t, const float* obs, const float* mean,
-                     const float* value, const float* log_std, uint64_t seed, float* env_actions, void* stream) {
-    RolloutArgs a;
-    int rc = rollout_args(h, rb, a, "ch_rollout_store");
-    if (rc) return rc;
-    if (t < 0 || t >= rb->n_steps) return fail(h, CH_ERR_INVALID, "ch_rollout_store: t outside [0, n_steps)");
-    if (!obs || !mean || !value || !log_std || !env_actions || !rb->obs || !rb->actions || !rb->values ||
-        !rb->log_probs || !rb->episode_starts || !rb->last_episode_starts)
-        return fail(h, CH_ERR_INVALID, "ch_rollout_store: NULL buffer");
-    if ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(rb->obs)) & 15)
-        return fail(h, CH_ERR_INVALID, "ch_rollout_store: obs buffers must be 16-byte aligned");
-    a.t = t; a.obs_now = obs; a.mean = mean; a.value = value; a.log_std = log_std; a.seed = seed;
-    a.env_actions = env_actions; a.copy_obs = 1;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, launch_rollout(a, 0, (hipStream_t)stream));
-    return CH_OK;
-}
-
-int ch_rollout_post(ch_handle* h, const ch_rollout* rb, int32_t t, const float* reward, const uint8_t* terminated,
-                    const uint8_t* truncated, const float* terminal_value, float gamma, void* stream) {
-    RolloutArgs a;
-    int rc = rollout_args(h, rb, a, "ch_rollout_post");
-    if (rc) return rc;
-    if (t < 0 || t >= rb->n_steps) return fail(h, CH_ERR_INVALID, "ch_rollout_post: t outside [0, n_steps)");
-    if (!reward || !terminated || !truncated || !rb->rewards || !rb->last_episode_starts)
-        return fail(h, CH_ERR_INVALID, "ch_rollout_post: NULL buffer");
-    a.t = t; a.reward = reward; a.terminated = terminated; a.truncated = truncated; a.terminal_value = terminal_value;
-    a.gamma = gamma;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, launch_rollout(a, 1, (hipStream_t)stream));
-    return CH_OK;
-}
-
-int ch_rollout_gae(ch_handle* h, const ch_rollout* rb, const float* last_value, float gamma, float gae_lambda,
-                   void* stream) {
-    RolloutArgs a;
-    int rc = rollout_args(h, rb, a, "ch_rollout_gae");
-    if (rc) return rc;
-    if (!last_value || !rb->rewards || !rb->values || !rb->episode_starts || !rb->advantages || !rb->returns)
-        return fail(h, CH_ERR_INVALID, "ch_rollout_gae: NULL buffer");
-    a.value = last_value; a.gamma = gamma;
-    a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, launch_rollout(a, 2, (hipStream_t)stream));
-    return CH_OK;
-}
-
-int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
-                       const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
-                       int32_t bootstrap_truncated, void* stream) {
-    RolloutArgs ra;
-    int rc = rollout_args(h, rb, ra, "ch_rollout_collect");
-    if (rc) return rc;
-    if (!io || !io->step || !io->mean || !io->env_actions || !log_std || !actor || (critic && !io->value))
-        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: NULL argument");
-    const ch_step_io* sio = io->step;
-    if (!sio->obs || !sio->reward || !sio->terminated || !sio->truncated || !sio->terminal_obs || !sio->reset_happened ||
-        (bootstrap_truncated && !io->terminal_value))
-        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: the step buffers (obs, reward, terminated, truncated, "
-                                       "terminal_obs, reset_happened) and terminal_value are required");
-    if (!rb->obs || !rb->actions || !rb->rewards || !rb->episode_starts || !rb->values || !rb->log_probs ||
-        !rb->advantages || !rb->returns || !rb->last_episode_starts)
-        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: NULL rollout buffer array");
-    if ((reinterpret_cast<uintptr_t>(sio->obs) | reinterpret_cast<uintptr_t>(rb->obs)) & 15)
-        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: obs buffers must be 16-byte aligned");
-    // critic == NULL: `actor` is a fused actor-critic (both heads in one net, output act_dim + 1 wide: the action
-    // mean, then the value); one forward per step reads the observation once.  io->mean is then its
-    // [rows][act_dim + 1] output and io->terminal_value a [rows][act_dim + 1] one for the terminal observations.
-    const bool fused = critic == nullptr;
-    const int out_w = fused ? rb->act_dim + 1 : rb->act_dim;
-    if (actor->dims[actor->n_layers] != out_w || (!fused && critic->dims[critic->n_layers] != 1))
-        return fail(h, CH_ERR_INVALID, fused ? "ch_rollout_collect: a fused actor-critic's output must be act_dim + 1 wide"
-                                             : "ch_rollout_collect: actor output must be act_dim wide, critic output 1");
-    hipStream_t st = (hipStream_t)stream;
-    ch_step_io s = *sio;
-    s.actions = io->env_actions; s.actions_out = nullptr;
-    s.flags = (s.flags & ~CH_STEP_RANDOM_ACTIONS) | CH_STEP_AUTORESET;
-    const ch_mlp* vnet = fused ? actor : critic;
-    float* value = fused ? io->mean + rb->act_dim : io->value;
-    float* tv_out = io->terminal_value;
-    const float* tval = fused ? io->terminal_value + rb->act_dim : io->terminal_value;
-    RolloutArgs a = ra;
-    a.mean_ld = out_w; a.value_ld = fused ? out_w : 1; a.tv_ld = fused ? out_w : 1;
-    // each step's post (reward + gamma V(terminal obs), next episode start) runs in the next step's store, the
-    // last one in the GAE kernel: the step outputs and terminal values it reads are still that step's then
-    a.post_prev = 1;
-    a.reward = sio->reward; a.terminated = sio->terminated; a.truncated = sio->truncated;
-    a.terminal_value = bootstrap_truncated ? tval : nullptr; a.gamma = gamma;
-    a.obs_now = sio->obs; a.mean = io->mean; a.value = value; a.log_std = log_std; a.seed = seed;
-    a.env_actions = io->env_actions;
-    // The step writes its observations straight into the buffer's next slot (obs[t + 1]; the last step into the
-    // env's own obs buffer): the obs of step t > 0 is already in place when it is stored, and only obs[0] is copied
-    // (a v2 step into a buffer other than the one it wrote last writes every block in full, ch_step's obs_zero_ptr).
-    // The actor and critic on obs[t + 1] go out as one launch (launch_mlp_multi; their workgroups share the CUs,
-    // so each forward's latencies hide behind the other's matrix work).  The truncation bootstrap is deferred: the
-    // post of step t queues the terminal observations of the envs that were truncated and not terminated, and
-    // every kTvEvery steps one forward over the queue gives their values, added to those rewards rows (the queue
-    // holds at most kTvEvery * E rows).  Per step that leaves two launches with separate nets (forwards with the
-    // store in their epilogues, step) and three with a fused net or CH_ROLLOUT_STORE_KERNEL=1 (forward, store, step).
-    // (the period: 16 steps, fewer when the queue would pass 1 GiB -- one flush is a whole forward's latency, ~20 us
-    // at configs[2]'s size, whatever the queue holds)
-    const int kTvEvery = (int)std::min<long long>(16, std::max<long long>(1, (1LL << 30) / ((long long)h->E * ra.obs_dim * 4)));
-    const bool copy_each = (h->rollout_path & 1) != 0;
-    const size_t slot = (size_t)h->E * (size_t)ra.obs_dim;
-    auto obs_at = [&](int32_t t) { return (t == 0 || t == rb->n_steps || copy_each) ? sio->obs : rb->obs + (size_t)t * slot; };
-    MlpArgs fa, fc, ftv;
-    if ((rc = policy_args(h, actor, sio->obs, io->mean, fa, "ch_rollout_collect (actor)"))) return rc;
-    if (!fused && (rc = policy_args(h, critic, sio->obs, io->value, fc, "ch_rollout_collect (critic)"))) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const long long cap = (long long)h->E * kTvEvery;
-    RolloutArgs ap = a;   // k_rollout_apply over the queue
-    if (bootstrap_truncated) {
-        const size_t nobs = (size_t)cap * ra.obs_dim, nval = (size_t)cap * out_w;
-        if (h->tv_obs_n < nobs) {
-            if (h->tv_obs) HIP_TRY(h, hipFree(h->tv_obs));
-            h->tv_obs = nullptr;
-            HIP_TRY(h, hipMalloc(&h->tv_obs, sizeof(float) * nobs));
-            if (h->tv_row) HIP_TRY(h, hipFree(h->tv_row));
-            h->tv_row = nullptr;
-            HIP_TRY(h, hipMalloc(&h->tv_row, sizeof(long long) * (size_t)cap));
-            h->tv_obs_n = nobs;
-        }
-        if (h->tv_val_n < nval) {
-            if (h->tv_val) HIP_TRY(h, hipFree(h->tv_val));
-            h->tv_val = nullptr;
-            HIP_TRY(h, hipMalloc(&h->tv_val, sizeof(float) * nval));
-            h->tv_val_n = nval;
-        }
-        if (!h->tv_count) HIP_TRY(h, hipMalloc(&h->tv_count, sizeof(int)));
-        HIP_TRY(h, hipMemsetAsync(h->tv_count, 0, sizeof(int), st));
-        // V(terminal obs) over the queue: whole (12, 86) blocks, zero past the constructor's drones
-        std::string err;
-        if ((rc = mlp_args(vnet, h->tv_obs, cap, h->tv_val, ftv, err))) return fail(h, rc, "ch_rollout_collect: " + err);
-        ftv.rows_dev = h->tv_count;
-        ftv.kcap = std::min(ftv.dims[0], h->NC * 86);
-        a.defer = 1; a.term_obs = sio->terminal_obs; a.tv_obs = h->tv_obs; a.tv_count = h->tv_count; a.tv_row = h->tv_row;
-        a.terminal_value = nullptr;
-        ap = a;
-        ap.rows = cap;
-        ap.terminal_value = h->tv_val + (fused ? rb->act_dim : 0);
-        ap.tv_ld = fused ? out_w : 1;   // the value net's output width
-        ap.v_col = fused ? rb->act_dim : 0;
-    }
-    // the flush: V over the queue with the reward update in the forward's epilogue (kRoleTvApply), or (a net k_mlp2
-    // does not take) the forward into tv_val and k_rollout_apply; then the queue is emptied
-    const bool tv_epi = bootstrap_truncated && mlp_multi_fits(&ftv, 1) && !(h->rollout_path & 2);
-    auto flush = [&]() -> hipError_t {
-        hipError_t e;
-        if (tv_epi) {
-            const int role = kRoleTvApply;
-            e = launch_mlp_multi(&ftv, 1, st, &role, &ap);
-        } else {
-            e = launch_mlp_multi(&ftv, 1, st);
-            if (e == hipSuccess) e = launch_rollout(ap, 3, st);
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(h->tv_count, 0, sizeof(int), st);
-        return e;
-    };
-    MlpArgs segs[2];
-    segs[0] = fa; segs[1] = fc;
-    const bool no_epi = (h->rollout_path & 2) != 0;
-    if (!fused && !no_epi && mlp_multi_fits(segs, 2)) {
-        // Two launches per step: the actor and critic forwards with the store folded into their epilogues (the
-        // actor's samples its actions, log-probabilities and env actions; the critic's writes the values, the
-        // previous step's post and the episode starts, and at t = 0 copies obs[0]), then the step.
-        // With the fused step (rollout_path bit 2: CH_FUSED_ACTOR=1 or ch__set_rollout_path; bit 3 forbids it) the
-        // actor forward of step t + 1 runs in the step kernel of step t, in the workgroup that wrote those
-        // observations (k_step2_actor), and the critic goes out alone: the same work in the same stream order.
-        const int roles[2] = {kRoleSample, kRoleValue};
-        const bool fuse = (h->rollout_path & 4) && !(h->rollout_path & 8) &&
-                          step_actor(h, &s, st, segs[0], a, false) == hipSuccess;
-        RolloutArgs ro = a;
-        for (int32_t t = 0; t < rb->n_steps; ++t) {
-            segs[0].x = segs[1].x = obs_at(t);
-            ro.t = t;
-            ro.copy_obs = t == 0 || copy_each;
-            if (fuse && t > 0) HIP_TRY(h, launch_mlp_multi(&segs[1], 1, st, &roles[1], &ro));   // the critic
-            else HIP_TRY(h, launch_mlp_multi(segs, 2, st, roles, &ro));
-            if (bootstrap_truncated && t > 0 && t % kTvEvery == 0) HIP_TRY(h, flush());
-            s.obs = (t + 1 < rb->n_steps && !copy_each) ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
-            if (fuse && t + 1 < rb->n_steps) {
-                MlpArgs fa = segs[0];
-                fa.x = obs_at(t + 1);   // = s.obs
-                RolloutArgs rn = ro;
-                rn.t = t + 1;
-                const hipError_t e = step_actor(h, &s, st, fa, rn, true);
-                if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_rollout_collect fused step: ") + hipGetErrorString(e));
-            } else if ((rc = ch_step(h, &s, stream))) {
-                return rc;
-            }
-        }
-        // the last step's post (and queue) and flush, V(obs after the last step), GAE without a post of its own
-        RolloutArgs pa = a;
-        pa.t = rb->n_steps;
-        pa.post_only = 1;
-        HIP_TRY(h, launch_rollout(pa, 0, st));
-        if (bootstrap_truncated) HIP_TRY(h, flush());
-        MlpArgs fv = fc;
-        fv.x = obs_at(rb->n_steps);
-        HIP_TRY(h, launch_mlp_multi(&fv, 1, st));
-        a.post_prev = 0;
-        a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
-        HIP_TRY(h, launch_rollout(a, 2, st));
-        return CH_OK;
-    }
-    HIP_TRY(h, launch_mlp_multi(segs, fused ? 1 : 2, st));
-    for (int32_t t = 0; t < rb->n_steps; ++t) {
-        // SB3 collect_rollouts, one step of every env: policy(obs) -> sample, log-prob, value -> env.step ->
-        // bootstrap truncated rewards with V(terminal obs) -> buffer (OnPolicyAlgorithm.collect_rollouts)
-        a.t = t;
-        a.copy_obs = t == 0 || copy_each;
-        HIP_TRY(h, launch_rollout(a, 0, st));   // (with the post of step t - 1)
-        if (bootstrap_truncated && t > 0 && t % kTvEvery == 0) HIP_TRY(h, flush());
-        s.obs = (t + 1 < rb->n_steps && !copy_each) ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
-        if ((rc = ch_step(h, &s, stream))) return rc;
-        int n = 0;
-        if (t + 1 < rb->n_steps) {
-            fa.x = fc.x = obs_at(t + 1);
-            segs[n++] = fa;
-            if (!fused) segs[n++] = fc;
-        } else {   // the last observations' values: GAE's last_value
-            MlpArgs fv = fused ? fa : fc;
-            fv.x = obs_at(t + 1);
-            segs[n++] = fv;
-        }
-        HIP_TRY(h, launch_mlp_multi(segs, n, st));
-    }
-    if (bootstrap_truncated) {
-        // the last step's post (and queue), the last flush; GAE then runs without a post of its own
-        RolloutArgs pa = a;
-        pa.t = rb->n_steps;
-        pa.post_only = 1;
-        HIP_TRY(h, launch_rollout(pa, 0, st));
-        HIP_TRY(h, flush());
-        a.post_prev = 0;
-    }
-    a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
-    HIP_TRY(h, launch_rollout(a, 2, st));
-    return CH_OK;
-}
-
-int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
-                            const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream) {
-    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL handle");
-    if (h->cfg.mode != CH_MODE_MARL)
-        return fail(h, CH_ERR_UNSUPPORTED, "ch_marl_rollout_collect: the per-agent rollout is for MARL handles");
-    if (!rb || !io || !io->step || !policy || !value || !io->policy_out || !io->value_out || !io->env_actions)
-        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL argument");
-    if (rb->n_steps < 1 || rb->act_dim != 4)
-        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: n_steps >= 1 and act_dim = 4 (one VEL action per agent)");
-    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->values || !rb->rewards || !rb->agent_mask || !rb->terminated ||
-        !rb->truncated || !rb->advantages || !rb->returns || !rb->last_values)
-        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL rollout buffer array");
-    const ch_step_io* sio = io->step;
-    if (!sio->obs || !sio->reward || !sio->terminated || !sio->truncated)
-        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: the step buffers obs, reward, terminated, truncated are required");
-    if ((reinterpret_cast<uintptr_t>(sio->obs) | reinterpret_cast<uintptr_t>(rb->obs)) & 15)
-        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: obs buffers must be 16-byte aligned");
-    if (policy->dims[policy->n_layers] != 2 * rb->act_dim || value->dims[value->n_layers] != 1)
-        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: the policy must output 2 * act_dim (mean, log_std), the value net 1");
-    int rc;
-    MlpArgs fp, fv;
-    if ((rc = policy_args(h, policy, sio->obs, io->policy_out, fp, "ch_marl_rollout_collect (policy)"))) return rc;
-    if ((rc = policy_args(h, value, sio->obs, io->value_out, fv, "ch_marl_rollout_collect (value)"))) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    MarlArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.T = rb->n_steps; a.A = rb->act_dim; a.N = h->NC; a.E = h->E; a.rows = h->E * h->NC;
-    a.env_n = h->envi; a.env_active = h->envi + 7 * h->E;
-    a.pol = io->policy_out; a.val = io->value_out; a.seed = seed; a.post_prev = 1;
-    a.reward = sio->reward; a.term = sio->terminated; a.trunc = sio->truncated;
-    a.gamma = gamma; a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);
-    a.obs = rb->obs; a.actions = rb->actions; a.log_probs = rb->log_probs; a.values = rb->values; a.rewards = rb->rewards;
-    a.advantages = rb->advantages; a.returns = rb->returns; a.last_values = rb->last_values; a.env_actions = io->env_actions;
-    a.mask = rb->agent_mask; a.terminated = rb->terminated; a.truncated = rb->truncated;
-    // the step writes its observations straight into the buffer's next slot (a step into a buffer other than the one
-    // it wrote last writes every block in full); the last step into the env's own buffer.  No terminal observations:
-    // an agent's trajectory ends only where it terminates (no bootstrap), so the reset path needs no copy.
-    ch_step_io s = *sio;
-    s.actions = io->env_actions; s.actions_out = nullptr; s.terminal_obs = nullptr;
-    s.flags = (s.flags & ~CH_STEP_RANDOM_ACTIONS) | CH_STEP_AUTORESET;
-    const size_t slot = (size_t)a.rows * 86;
-    MlpArgs segs[2];
-    for (int32_t t = 0; t < rb->n_steps; ++t) {
-        const float* x = t == 0 ? sio->obs : rb->obs + (size_t)t * slot;
-        segs[0] = fp; segs[1] = fv;
-        segs[0].x = segs[1].x = x;
-        HIP_TRY(h, launch_mlp_multi(segs, 2, st));
-        a.t = t;
-        a.obs_now = t == 0 ? sio->obs : nullptr;
-        HIP_TRY(h, launch_marl_rollout(a, 0, st));
-        s.obs = t + 1 < rb->n_steps ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
-        if ((rc = ch_step(h, &s, stream))) return rc;
-    }
-    // V(obs after the last step) -> last_values, the last step's post, GAE
-    fv.x = sio->obs;
-    HIP_TRY(h, launch_mlp_multi(&fv, 1, st));
-    HIP_TRY(h, launch_marl_rollout(a, 1, st));
     return CH_OK;
 }
 
@@ -1371,17 +835,17 @@ int ch_outputs_to_host(ch_handle* h, const ch_step_io* io, ch_host_out* out, voi
     const int64_t E = h->E;
     const size_t blk = (size_t)h->rows * 86, live = (size_t)h->NC * 86;   // floats per block / in its first NC rows
     if (io->reset_happened) {
-        if (!h->st_count) {
-            HIP_TRY(h, hipMalloc(&h->st_count, sizeof(long long)));
-            HIP_TRY(h, hipMalloc(&h->st_env, sizeof(long long) * E));
-            HIP_TRY(h, hipMalloc(&h->st_stats, sizeof(double) * 2 * E));
-            HIP_TRY(h, hipMalloc(&h->st_obs, sizeof(float) * blk * E));
-            HIP_TRY(h, hipHostMalloc(&h->st_count_host, sizeof(long long), hipHostMallocDefault));
+        if (!h->st.count) {
+            HIP_TRY(h, hipMalloc(&h->st.count, sizeof(long long)));
+            HIP_TRY(h, hipMalloc(&h->st.env, sizeof(long long) * E));
+            HIP_TRY(h, hipMalloc(&h->st.stats, sizeof(double) * 2 * E));
+            HIP_TRY(h, hipMalloc(&h->st.obs, sizeof(float) * blk * E));
+            HIP_TRY(h, hipHostMalloc(&h->st.count_host, sizeof(long long), hipHostMallocDefault));
         }
         HIP_TRY(h, launch_stage_ended(E, io->reset_happened, out->ended_obs ? io->terminal_obs : nullptr,
-                                      out->ended_stats ? io->episode_stats : nullptr, (int)blk, h->st_count, h->st_env,
-                                      h->st_stats, h->st_obs, st));
-        HIP_TRY(h, hipMemcpyAsync(h->st_count_host, h->st_count, sizeof(long long), hipMemcpyDeviceToHost, st));
+                                      out->ended_stats ? io->episode_stats : nullptr, (int)blk, h->st.count, h->st.env,
+                                      h->st.stats, h->st.obs, st));
+        HIP_TRY(h, hipMemcpyAsync(h->st.count_host, h->st.count, sizeof(long long), hipMemcpyDeviceToHost, st));
     }
     // the first NC rows of every block (CTDE: rows >= NC are always zero; MARL: R = NC, one contiguous copy)
     if (live == blk)
@@ -1398,26 +862,26 @@ int ch_outputs_to_host(ch_handle* h, const ch_step_io* io, ch_host_out* out, voi
         HIP_TRY(h, hipMemcpyAsync(out->agent_active, io->agent_active, (size_t)h->NC * E, hipMemcpyDeviceToHost, st));
     // the ended envs' lists: a speculative first part sized from the recent counts (the usual case: a few envs end per
     // step -- at C4 under random actions ~20, in a training rollout ~3), the rest after the count
-    const int64_t cap = std::min<int64_t>(E, 2 * std::max<int64_t>(h->ended_last, (int64_t)h->ended_mean) + 8);
+    const int64_t cap = std::min<int64_t>(E, 2 * std::max<int64_t>(h->st.ended_last, (int64_t)h->st.ended_mean) + 8);
     auto copy_ended = [&](int64_t lo, int64_t hi) -> int {
         if (hi <= lo) return CH_OK;
         if (out->ended_env)
-            HIP_TRY(h, hipMemcpyAsync(out->ended_env + lo, h->st_env + lo, sizeof(long long) * (hi - lo), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipMemcpyAsync(out->ended_env + lo, h->st.env + lo, sizeof(long long) * (hi - lo), hipMemcpyDeviceToHost, st));
         if (out->ended_stats)
-            HIP_TRY(h, hipMemcpyAsync(out->ended_stats + 2 * lo, h->st_stats + 2 * lo, sizeof(double) * 2 * (hi - lo),
+            HIP_TRY(h, hipMemcpyAsync(out->ended_stats + 2 * lo, h->st.stats + 2 * lo, sizeof(double) * 2 * (hi - lo),
                                       hipMemcpyDeviceToHost, st));
         if (out->ended_obs)
-            HIP_TRY(h, hipMemcpyAsync(out->ended_obs + blk * lo, h->st_obs + blk * lo, sizeof(float) * blk * (hi - lo),
+            HIP_TRY(h, hipMemcpyAsync(out->ended_obs + blk * lo, h->st.obs + blk * lo, sizeof(float) * blk * (hi - lo),
                                       hipMemcpyDeviceToHost, st));
         return CH_OK;
     };
     int rc = CH_OK;
     if (io->reset_happened && (rc = copy_ended(0, cap))) return rc;
     HIP_TRY(h, hipStreamSynchronize(st));
-    out->ended_count = io->reset_happened ? *h->st_count_host : 0;
+    out->ended_count = io->reset_happened ? *h->st.count_host : 0;
     if (io->reset_happened) {
-        h->ended_last = out->ended_count;
-        h->ended_mean = 0.9 * h->ended_mean + 0.1 * (double)out->ended_count;
+        h->st.ended_last = out->ended_count;
+        h->st.ended_mean = 0.9 * h->st.ended_mean + 0.1 * (double)out->ended_count;
     }
     if (out->ended_count > cap) {
         if ((rc = copy_ended(cap, out->ended_count))) return rc;

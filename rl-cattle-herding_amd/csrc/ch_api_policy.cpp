@@ -1,0 +1,449 @@
+// ch_api_policy.cpp — the policy half of the C ABI (see include/cattleherd.h): MLP packing and forwards on device
+// buffers (ch_policy.hip), the on-device PPO rollout buffer and its collection loop, the per-agent MARL rollout
+// (ch_aux.hip).  It reaches the env through ch_step and step_actor (ch_api.cpp) and a few fields of the handle.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "ch_handle.h"
+
+using namespace ch;
+
+static int launch_or_fail(ch_handle* h, const char* who, hipError_t e) {
+    if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string(who) + " launch: " + hipGetErrorString(e));
+    return CH_OK;
+}
+
+static int mlp_args(const ch_mlp* net, const float* x, int64_t rows, float* y, MlpArgs& a, std::string& err) {
+    if (!net || !x || !y) { err = "NULL argument"; return CH_ERR_INVALID; }
+    if (net->n_layers < 1 || net->n_layers > 4) { err = "n_layers must be 1..4"; return CH_ERR_INVALID; }
+    if (rows < 0) { err = "rows < 0"; return CH_ERR_INVALID; }
+    std::memset(&a, 0, sizeof(a));
+    a.layers = net->n_layers;
+    for (int i = 0; i <= net->n_layers; ++i) {
+        a.dims[i] = net->dims[i];
+        if (net->dims[i] < 1 || (i > 0 && net->dims[i] > 256)) { err = "layer widths must be 1..256"; return CH_ERR_UNSUPPORTED; }
+    }
+    for (int i = 0; i < net->n_layers; ++i) {
+        if (!net->weight[i]) { err = "NULL weight"; return CH_ERR_INVALID; }
+        a.w[i] = net->weight[i]; a.b[i] = net->bias[i];
+    }
+    if (net->hidden_act < CH_ACT_NONE || net->hidden_act > CH_ACT_RELU) { err = "unknown activation"; return CH_ERR_INVALID; }
+    a.hidden_act = net->hidden_act; a.clip = net->clip != 0; a.lo = net->lo; a.hi = net->hi;
+    a.x = x; a.rows = rows; a.y = y; a.rows_per_env = 1;
+    a.kcap = net->dims[0];
+    // float4 weight loads need 16-B aligned rows of a multiple of 8 floats (k_mlp2 reads 8 per lane), inputs 4
+    for (int i = 0; i < net->n_layers; ++i)
+        if (net->dims[i] % 8 == 0 && (reinterpret_cast<uintptr_t>(net->weight[i]) & 15) == 0) a.vec_w |= 1 << i;
+    if (net->dims[0] % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) a.vec_w |= 1 << 7;
+    // block-diagonal layers the kernel can skip by whole K-pair groups (ch_mlp.split_*); others run dense
+    for (int i = 1; i < net->n_layers; ++i) {
+        const int so = net->split_out[i], si = net->split_in[i];
+        if (so > 0 && so < net->dims[i + 1] && so % 32 == 0 && si > 0 && si < net->dims[i] && si % 128 == 0) {
+            a.split_out[i] = so; a.split_in[i] = si;
+        }
+    }
+    if (net->packed) {
+        if (reinterpret_cast<uintptr_t>(net->packed) & 15) { err = "packed weights must be 16-byte aligned"; return CH_ERR_INVALID; }
+        a.packed = net->packed;
+        mlp_packed_floats(a.layers, a.dims, a.pk_off, a.pk_pairs);
+    }
+    return CH_OK;
+}
+
+// the forward of `net` on a handle's observation buffer: one row per env (CTDE) or agent (MARL), live widths from
+// NUM_DRONES (envi row 0)
+static int policy_args(ch_handle* h, const ch_mlp* net, const float* obs, float* y, MlpArgs& a, const char* who) {
+    const bool marl = h->cfg.mode == CH_MODE_MARL;
+    const int64_t rows = marl ? h->E * h->NC : h->E;
+    const int want = marl ? 86 : h->rows * 86;
+    if (net && net->dims[0] != want)
+        return fail(h, CH_ERR_INVALID, std::string(who) + ": dims[0] must be " + std::to_string(want) + " for this handle");
+    std::string err;
+    const int rc = mlp_args(net, obs, rows, y, a, err);
+    if (rc) return fail(h, rc, std::string(who) + ": " + err);
+    a.env_n = h->envi;   // envi row 0: NUM_DRONES of the episode each env is in
+    a.rows_per_env = marl ? h->NC : 1;
+    a.k_unit = 86;
+    a.kcap = std::min(a.dims[0], marl ? 86 : h->NC * 86);   // NUM_DRONES <= the constructor's drones
+    return CH_OK;
+}
+
+// the step both collections run: the caller's io with the sampled env actions in, auto-reset on, no random actions
+static ch_step_io collect_step_io(const ch_step_io* sio, const float* env_actions) {
+    ch_step_io s = *sio;
+    s.actions = env_actions; s.actions_out = nullptr;
+    s.flags = (s.flags & ~CH_STEP_RANDOM_ACTIONS) | CH_STEP_AUTORESET;
+    return s;
+}
+
+static int rollout_args(ch_handle* h, const ch_rollout* rb, RolloutArgs& a, const char* who) {
+    if (!h) return fail(nullptr, CH_ERR_INVALID, std::string(who) + ": NULL handle");
+    if (!rb) return fail(h, CH_ERR_INVALID, std::string(who) + ": NULL rollout buffer");
+    if (h->cfg.mode != CH_MODE_CTDE)
+        return fail(h, CH_ERR_UNSUPPORTED, std::string(who) + ": the SB3 rollout buffer is for CTDE handles");
+    // the env reads a (num_drones, 4) action per env (ch_step: float4 [e * num_drones + k]), so the policy must
+    // produce at least num_drones * 4 outputs (SB3: Box((NUM_DRONES, 4)) or the reference's (12, 4))
+    if (rb->n_steps < 1 || rb->act_dim < h->NC * 4 || rb->act_dim > 256)
+        return fail(h, CH_ERR_INVALID, std::string(who) + ": n_steps >= 1 and num_drones * 4 = " +
+                                           std::to_string(h->NC * 4) + " <= act_dim <= 256 required");
+    std::memset(&a, 0, sizeof(a));
+    a.T = rb->n_steps; a.rows = h->E; a.obs_dim = h->rows * 86; a.act_dim = rb->act_dim;
+    a.env_act_dim = h->NC * 4;
+    a.mean_ld = rb->act_dim; a.value_ld = 1; a.tv_ld = 1; a.post_prev = 0;
+    a.obs = rb->obs; a.actions = rb->actions; a.rewards = rb->rewards; a.episode_starts = rb->episode_starts;
+    a.values = rb->values; a.log_probs = rb->log_probs; a.advantages = rb->advantages; a.returns = rb->returns;
+    a.last_episode_starts = rb->last_episode_starts;
+    return CH_OK;
+}
+
+// a device buffer of at least `want` bytes (contents not kept): freed and allocated again when it is smaller
+static int grow(ch_handle* h, void** p, size_t* have, size_t want) {
+    if (*have >= want) return CH_OK;
+    if (*p) HIP_TRY(h, hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    HIP_TRY(h, hipMalloc(p, want));
+    *have = want;
+    return CH_OK;
+}
+
+extern "C" {
+
+// diagnostics: k_mlp2 writes wave 0's phase clocks of every workgroup to dev[blockIdx][16] (NULL: off); the fused
+// step + actor kernel (k_step2_actor) writes its forward's clocks and wall-clock slots 13-15 to rows [grid, 2 grid),
+// so a buffer for a collection on the fused path holds 2 x 16 x (E / 16) entries (tools/fused_probe.py trace)
+int ch__set_mlp_tstamp(long long* dev) {
+    g_mlp_tstamp = dev;
+    return CH_OK;
+}
+
+/* Internal (tests / diagnostics): ch_rollout_collect's path, bit 0 copy each step's observation into the buffer
+ * (CH_ROLLOUT_COPY=1), bit 1 the stand-alone store kernel instead of the forward epilogues (CH_ROLLOUT_STORE_KERNEL=1),
+ * bit 2 the actor forward fused into the step (CH_FUSED_ACTOR=1), bit 3 never fused. */
+int ch__set_rollout_path(ch_handle* h, int32_t bits) {
+    if (!h || bits < 0 || bits > 15) return CH_ERR_INVALID;
+    h->ro.path = bits;
+    return CH_OK;
+}
+
+/* Internal: the handle's current rollout path bits (ch__set_rollout_path), or -1 for a null handle. */
+int ch__get_rollout_path(const ch_handle* h) { return h ? h->ro.path : -1; }
+
+/* Internal (tests): steps ch_rollout_collect has launched as the fused step + actor kernel on this handle. */
+int64_t ch__rollout_fused_steps(const ch_handle* h) { return h ? (int64_t)h->ro.fused_steps : -1; }
+
+int64_t ch_mlp_packed_size(const ch_mlp* net) {
+    if (!net || net->n_layers < 1 || net->n_layers > 4) return -1;
+    for (int i = 0; i <= net->n_layers; ++i)
+        if (net->dims[i] < 1 || (i > 0 && net->dims[i] > 256)) return -1;
+    return mlp_packed_floats(net->n_layers, net->dims, nullptr, nullptr);
+}
+
+int ch_mlp_pack(const ch_mlp* net, float* dst, void* stream) {
+    MlpArgs a;
+    std::string err;
+    float one = 0.0f;
+    const int rc = mlp_args(net, &one, 0, &one, a, err);
+    if (rc) return fail(nullptr, rc, "ch_mlp_pack: " + err);
+    if (!dst || (reinterpret_cast<uintptr_t>(dst) & 15)) return fail(nullptr, CH_ERR_INVALID, "ch_mlp_pack: dst NULL or not 16-byte aligned");
+    return launch_or_fail(nullptr, "ch_mlp_pack", launch_mlp_pack(a, dst, (hipStream_t)stream));
+}
+
+int ch_mlp_forward(const ch_mlp* net, const float* x, int64_t rows, float* y, void* stream) {
+    MlpArgs a;
+    std::string err;
+    const int rc = mlp_args(net, x, rows, y, a, err);
+    if (rc) return fail(nullptr, rc, "ch_mlp_forward: " + err);
+    return launch_or_fail(nullptr, "ch_mlp_forward", launch_mlp(a, (hipStream_t)stream));
+}
+
+int ch_mlp_forward_masked(const ch_mlp* net, const float* x, int64_t rows, const uint8_t* row_mask, float* y,
+                          void* stream) {
+    MlpArgs a;
+    std::string err;
+    const int rc = mlp_args(net, x, rows, y, a, err);
+    if (rc) return fail(nullptr, rc, "ch_mlp_forward_masked: " + err);
+    if (!row_mask) return fail(nullptr, CH_ERR_INVALID, "ch_mlp_forward_masked: NULL row mask");
+    a.row_mask = row_mask;
+    return launch_or_fail(nullptr, "ch_mlp_forward_masked", launch_mlp(a, (hipStream_t)stream));
+}
+
+int ch_policy_forward(ch_handle* h, const ch_mlp* net, const float* obs, float* y, void* stream) {
+    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_policy_forward: NULL handle");
+    MlpArgs a;
+    const int rc = policy_args(h, net, obs, y, a, "ch_policy_forward");
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_or_fail(h, "ch_policy_forward", launch_mlp(a, (hipStream_t)stream));
+}
+
+int ch_rollout_store(ch_handle* h, const ch_rollout* rb, int32_t t, const float* obs, const float* mean,
+                     const float* value, const float* log_std, uint64_t seed, float* env_actions, void* stream) {
+    RolloutArgs a;
+    int rc = rollout_args(h, rb, a, "ch_rollout_store");
+    if (rc) return rc;
+    if (t < 0 || t >= rb->n_steps) return fail(h, CH_ERR_INVALID, "ch_rollout_store: t outside [0, n_steps)");
+    if (!obs || !mean || !value || !log_std || !env_actions || !rb->obs || !rb->actions || !rb->values ||
+        !rb->log_probs || !rb->episode_starts || !rb->last_episode_starts)
+        return fail(h, CH_ERR_INVALID, "ch_rollout_store: NULL buffer");
+    if ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(rb->obs)) & 15)
+        return fail(h, CH_ERR_INVALID, "ch_rollout_store: obs buffers must be 16-byte aligned");
+    a.t = t; a.obs_now = obs; a.mean = mean; a.value = value; a.log_std = log_std; a.seed = seed;
+    a.env_actions = env_actions; a.copy_obs = 1;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_rollout(a, 0, (hipStream_t)stream));
+    return CH_OK;
+}
+
+int ch_rollout_post(ch_handle* h, const ch_rollout* rb, int32_t t, const float* reward, const uint8_t* terminated,
+                    const uint8_t* truncated, const float* terminal_value, float gamma, void* stream) {
+    RolloutArgs a;
+    int rc = rollout_args(h, rb, a, "ch_rollout_post");
+    if (rc) return rc;
+    if (t < 0 || t >= rb->n_steps) return fail(h, CH_ERR_INVALID, "ch_rollout_post: t outside [0, n_steps)");
+    if (!reward || !terminated || !truncated || !rb->rewards || !rb->last_episode_starts)
+        return fail(h, CH_ERR_INVALID, "ch_rollout_post: NULL buffer");
+    a.t = t; a.reward = reward; a.terminated = terminated; a.truncated = truncated; a.terminal_value = terminal_value;
+    a.gamma = gamma;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_rollout(a, 1, (hipStream_t)stream));
+    return CH_OK;
+}
+
+int ch_rollout_gae(ch_handle* h, const ch_rollout* rb, const float* last_value, float gamma, float gae_lambda,
+                   void* stream) {
+    RolloutArgs a;
+    int rc = rollout_args(h, rb, a, "ch_rollout_gae");
+    if (rc) return rc;
+    if (!last_value || !rb->rewards || !rb->values || !rb->episode_starts || !rb->advantages || !rb->returns)
+        return fail(h, CH_ERR_INVALID, "ch_rollout_gae: NULL buffer");
+    a.value = last_value; a.gamma = gamma;
+    a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_rollout(a, 2, (hipStream_t)stream));
+    return CH_OK;
+}
+
+int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
+                       const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
+                       int32_t bootstrap_truncated, void* stream) {
+    RolloutArgs ra;
+    int rc = rollout_args(h, rb, ra, "ch_rollout_collect");
+    if (rc) return rc;
+    if (!io || !io->step || !io->mean || !io->env_actions || !log_std || !actor || (critic && !io->value))
+        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: NULL argument");
+    const ch_step_io* sio = io->step;
+    if (!sio->obs || !sio->reward || !sio->terminated || !sio->truncated || !sio->terminal_obs || !sio->reset_happened ||
+        (bootstrap_truncated && !io->terminal_value))
+        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: the step buffers (obs, reward, terminated, truncated, "
+                                       "terminal_obs, reset_happened) and terminal_value are required");
+    if (!rb->obs || !rb->actions || !rb->rewards || !rb->episode_starts || !rb->values || !rb->log_probs ||
+        !rb->advantages || !rb->returns || !rb->last_episode_starts)
+        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: NULL rollout buffer array");
+    if ((reinterpret_cast<uintptr_t>(sio->obs) | reinterpret_cast<uintptr_t>(rb->obs)) & 15)
+        return fail(h, CH_ERR_INVALID, "ch_rollout_collect: obs buffers must be 16-byte aligned");
+    // critic == NULL: `actor` is a fused actor-critic (both heads in one net, output act_dim + 1 wide: the action
+    // mean, then the value); one forward per step reads the observation once.  io->mean is then its
+    // [rows][act_dim + 1] output and io->terminal_value a [rows][act_dim + 1] one for the terminal observations.
+    const bool fused = critic == nullptr;
+    const int out_w = fused ? rb->act_dim + 1 : rb->act_dim;
+    if (actor->dims[actor->n_layers] != out_w || (!fused && critic->dims[critic->n_layers] != 1))
+        return fail(h, CH_ERR_INVALID, fused ? "ch_rollout_collect: a fused actor-critic's output must be act_dim + 1 wide"
+                                             : "ch_rollout_collect: actor output must be act_dim wide, critic output 1");
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t T = rb->n_steps;
+    ch_step_io s = collect_step_io(sio, io->env_actions);
+    const ch_mlp* vnet = fused ? actor : critic;
+    float* value = fused ? io->mean + rb->act_dim : io->value;
+    const float* tval = fused ? io->terminal_value + rb->act_dim : io->terminal_value;
+    RolloutArgs a = ra;
+    a.mean_ld = out_w; a.value_ld = fused ? out_w : 1; a.tv_ld = fused ? out_w : 1;
+    // each step's post (reward + gamma V(terminal obs), next episode start) runs in the next step's store, the
+    // last one in the GAE kernel: the step outputs and terminal values it reads are still that step's then
+    a.post_prev = 1;
+    a.reward = sio->reward; a.terminated = sio->terminated; a.truncated = sio->truncated;
+    a.terminal_value = bootstrap_truncated ? tval : nullptr; a.gamma = gamma;
+    a.obs_now = sio->obs; a.mean = io->mean; a.value = value; a.log_std = log_std; a.seed = seed;
+    a.env_actions = io->env_actions;
+    // The step writes its observations straight into the buffer's next slot (obs[t + 1]; the last step into the
+    // env's own obs buffer): the obs of step t > 0 is already in place when it is stored, and only obs[0] is copied
+    // (a v2 step into a buffer other than the one it wrote last writes every block in full, ch_step's obs_zero_ptr).
+    // The actor and critic on obs[t] go out as one launch (launch_mlp_multi; their workgroups share the CUs,
+    // so each forward's latencies hide behind the other's matrix work).  The truncation bootstrap is deferred: the
+    // post of step t queues the terminal observations of the envs that were truncated and not terminated, and
+    // every kTvEvery steps one forward over the queue gives their values, added to those rewards rows (the queue
+    // holds at most kTvEvery * E rows).  Per step that leaves two launches with separate nets (forwards with the
+    // store in their epilogues, step) and three with a fused net or CH_ROLLOUT_STORE_KERNEL=1 (forward, store, step).
+    // (the period: 16 steps, fewer when the queue would pass 1 GiB -- one flush is a whole forward's latency, ~20 us
+    // at configs[2]'s size, whatever the queue holds)
+    const int kTvEvery = (int)std::min<long long>(16, std::max<long long>(1, (1LL << 30) / ((long long)h->E * ra.obs_dim * 4)));
+    const bool copy_each = (h->ro.path & 1) != 0;
+    const size_t slot = (size_t)h->E * (size_t)ra.obs_dim;
+    auto obs_at = [&](int32_t t) { return (t == 0 || t == T || copy_each) ? sio->obs : rb->obs + (size_t)t * slot; };
+    const int nnet = fused ? 1 : 2;
+    MlpArgs segs[2], ftv;   // the actor (or the fused net) and the critic; V over the queue
+    if ((rc = policy_args(h, actor, sio->obs, io->mean, segs[0], "ch_rollout_collect (actor)"))) return rc;
+    if (!fused && (rc = policy_args(h, critic, sio->obs, io->value, segs[1], "ch_rollout_collect (critic)"))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const long long cap = (long long)h->E * kTvEvery;
+    RolloutArgs ap = a;   // k_rollout_apply over the queue
+    if (bootstrap_truncated) {
+        ch_rollout_state& q = h->ro;
+        if ((rc = grow(h, (void**)&q.tv_obs, &q.tv_obs_bytes, sizeof(float) * (size_t)cap * ra.obs_dim)) ||
+            (rc = grow(h, (void**)&q.tv_row, &q.tv_row_bytes, sizeof(long long) * (size_t)cap)) ||
+            (rc = grow(h, (void**)&q.tv_val, &q.tv_val_bytes, sizeof(float) * (size_t)cap * out_w)) ||
+            (rc = grow(h, (void**)&q.tv_count, &q.tv_count_bytes, sizeof(int))))
+            return rc;
+        HIP_TRY(h, hipMemsetAsync(q.tv_count, 0, sizeof(int), st));
+        // V(terminal obs) over the queue: whole (12, 86) blocks, zero past the constructor's drones
+        std::string err;
+        if ((rc = mlp_args(vnet, q.tv_obs, cap, q.tv_val, ftv, err))) return fail(h, rc, "ch_rollout_collect: " + err);
+        ftv.rows_dev = q.tv_count;
+        ftv.kcap = std::min(ftv.dims[0], h->NC * 86);
+        a.defer = 1; a.term_obs = sio->terminal_obs; a.tv_obs = q.tv_obs; a.tv_count = q.tv_count; a.tv_row = q.tv_row;
+        a.terminal_value = nullptr;
+        ap = a;
+        ap.rows = cap;
+        ap.terminal_value = q.tv_val + (fused ? rb->act_dim : 0);
+        ap.tv_ld = fused ? out_w : 1;   // the value net's output width
+        ap.v_col = fused ? rb->act_dim : 0;
+    }
+    // the flush: V over the queue with the reward update in the forward's epilogue (kRoleTvApply), or (a net k_mlp2
+    // does not take) the forward into tv_val and k_rollout_apply; then the queue is emptied
+    const bool tv_epi = bootstrap_truncated && mlp_multi_fits(&ftv, 1) && !(h->ro.path & 2);
+    auto flush = [&]() -> hipError_t {
+        hipError_t e;
+        if (tv_epi) {
+            const int role = kRoleTvApply;
+            e = launch_mlp_multi(&ftv, 1, st, &role, &ap);
+        } else {
+            e = launch_mlp_multi(&ftv, 1, st);
+            if (e == hipSuccess) e = launch_rollout(ap, 3, st);
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(h->ro.tv_count, 0, sizeof(int), st);
+        return e;
+    };
+    // What the paths differ in.  epi: two separate nets k_mlp2 takes, and no store kernel asked for (path bit 1) --
+    // the store is folded into the forwards' epilogues (the actor's samples its actions, log-probabilities and env
+    // actions; the critic's writes the values, the previous step's post and the episode starts, and at t = 0 copies
+    // obs[0]); otherwise the plain forwards are followed by k_rollout_store.  fuse (path bit 2: CH_FUSED_ACTOR=1 or
+    // ch__set_rollout_path; bit 3 forbids it): the actor forward of step t + 1 runs in the step kernel of step t, in
+    // the workgroup that wrote those observations (k_step2_actor), and the critic goes out alone: the same work in the
+    // same stream order.
+    const bool epi = !fused && !(h->ro.path & 2) && mlp_multi_fits(segs, 2);
+    const bool fuse = epi && (h->ro.path & 4) && !(h->ro.path & 8) && step_actor(h, &s, st, segs[0], a, false) == hipSuccess;
+    const int roles[2] = {kRoleSample, kRoleValue};
+    RolloutArgs ro = a;
+    for (int32_t t = 0; t < T; ++t) {
+        // SB3 collect_rollouts, one step of every env: policy(obs) -> sample, log-prob, value -> env.step ->
+        // bootstrap truncated rewards with V(terminal obs) -> buffer (OnPolicyAlgorithm.collect_rollouts)
+        segs[0].x = segs[1].x = obs_at(t);
+        ro.t = t;
+        ro.copy_obs = t == 0 || copy_each;
+        if (!epi) {
+            HIP_TRY(h, launch_mlp_multi(segs, nnet, st));
+            HIP_TRY(h, launch_rollout(ro, 0, st));   // (with the post of step t - 1)
+        } else if (fuse && t > 0) {
+            HIP_TRY(h, launch_mlp_multi(&segs[1], 1, st, &roles[1], &ro));   // the critic; step t - 1 ran the actor
+        } else {
+            HIP_TRY(h, launch_mlp_multi(segs, 2, st, roles, &ro));
+        }
+        if (bootstrap_truncated && t > 0 && t % kTvEvery == 0) HIP_TRY(h, flush());
+        s.obs = (t + 1 < T && !copy_each) ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
+        if (fuse && t + 1 < T) {
+            MlpArgs fa = segs[0];
+            fa.x = obs_at(t + 1);   // = s.obs
+            RolloutArgs rn = ro;
+            rn.t = t + 1;
+            const hipError_t e = step_actor(h, &s, st, fa, rn, true);
+            if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_rollout_collect fused step: ") + hipGetErrorString(e));
+        } else if ((rc = ch_step(h, &s, stream))) {
+            return rc;
+        }
+    }
+    // The tail: the last step's post (and queue) with the last flush, V(obs after the last step) = GAE's last_value,
+    // GAE.  The epilogue path posts before that forward, the others after it and only when bootstrapping -- without
+    // the bootstrap their GAE kernel runs the last post itself.
+    RolloutArgs pa = a;
+    pa.t = T;
+    pa.post_only = 1;
+    auto last_post = [&]() -> int {
+        HIP_TRY(h, launch_rollout(pa, 0, st));
+        if (bootstrap_truncated) HIP_TRY(h, flush());
+        return CH_OK;
+    };
+    if (epi && (rc = last_post())) return rc;
+    MlpArgs fv = segs[nnet - 1];
+    fv.x = obs_at(T);
+    HIP_TRY(h, launch_mlp_multi(&fv, 1, st));
+    if (!epi && bootstrap_truncated && (rc = last_post())) return rc;
+    a.post_prev = !epi && !bootstrap_truncated;
+    a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
+    HIP_TRY(h, launch_rollout(a, 2, st));
+    return CH_OK;
+}
+
+int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
+                            const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream) {
+    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL handle");
+    if (h->cfg.mode != CH_MODE_MARL)
+        return fail(h, CH_ERR_UNSUPPORTED, "ch_marl_rollout_collect: the per-agent rollout is for MARL handles");
+    if (!rb || !io || !io->step || !policy || !value || !io->policy_out || !io->value_out || !io->env_actions)
+        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL argument");
+    if (rb->n_steps < 1 || rb->act_dim != 4)
+        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: n_steps >= 1 and act_dim = 4 (one VEL action per agent)");
+    if (!rb->obs || !rb->actions || !rb->log_probs || !rb->values || !rb->rewards || !rb->agent_mask || !rb->terminated ||
+        !rb->truncated || !rb->advantages || !rb->returns || !rb->last_values)
+        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL rollout buffer array");
+    const ch_step_io* sio = io->step;
+    if (!sio->obs || !sio->reward || !sio->terminated || !sio->truncated)
+        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: the step buffers obs, reward, terminated, truncated are required");
+    if ((reinterpret_cast<uintptr_t>(sio->obs) | reinterpret_cast<uintptr_t>(rb->obs)) & 15)
+        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: obs buffers must be 16-byte aligned");
+    if (policy->dims[policy->n_layers] != 2 * rb->act_dim || value->dims[value->n_layers] != 1)
+        return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: the policy must output 2 * act_dim (mean, log_std), the value net 1");
+    int rc;
+    MlpArgs fp, fv;
+    if ((rc = policy_args(h, policy, sio->obs, io->policy_out, fp, "ch_marl_rollout_collect (policy)"))) return rc;
+    if ((rc = policy_args(h, value, sio->obs, io->value_out, fv, "ch_marl_rollout_collect (value)"))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    MarlArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.T = rb->n_steps; a.A = rb->act_dim; a.N = h->NC; a.E = h->E; a.rows = h->E * h->NC;
+    a.env_n = h->envi; a.env_active = h->envi + 7 * h->E;
+    a.pol = io->policy_out; a.val = io->value_out; a.seed = seed; a.post_prev = 1;
+    a.reward = sio->reward; a.term = sio->terminated; a.trunc = sio->truncated;
+    a.gamma = gamma; a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);
+    a.obs = rb->obs; a.actions = rb->actions; a.log_probs = rb->log_probs; a.values = rb->values; a.rewards = rb->rewards;
+    a.advantages = rb->advantages; a.returns = rb->returns; a.last_values = rb->last_values; a.env_actions = io->env_actions;
+    a.mask = rb->agent_mask; a.terminated = rb->terminated; a.truncated = rb->truncated;
+    // the step writes its observations straight into the buffer's next slot (a step into a buffer other than the one
+    // it wrote last writes every block in full); the last step into the env's own buffer.  No terminal observations:
+    // an agent's trajectory ends only where it terminates (no bootstrap), so the reset path needs no copy.
+    ch_step_io s = collect_step_io(sio, io->env_actions);
+    s.terminal_obs = nullptr;
+    const size_t slot = (size_t)a.rows * 86;
+    MlpArgs segs[2];
+    for (int32_t t = 0; t < rb->n_steps; ++t) {
+        const float* x = t == 0 ? sio->obs : rb->obs + (size_t)t * slot;
+        segs[0] = fp; segs[1] = fv;
+        segs[0].x = segs[1].x = x;
+        HIP_TRY(h, launch_mlp_multi(segs, 2, st));
+        a.t = t;
+        a.obs_now = t == 0 ? sio->obs : nullptr;
+        HIP_TRY(h, launch_marl_rollout(a, 0, st));
+        s.obs = t + 1 < rb->n_steps ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
+        if ((rc = ch_step(h, &s, stream))) return rc;
+    }
+    // V(obs after the last step) -> last_values, the last step's post, GAE
+    fv.x = sio->obs;
+    HIP_TRY(h, launch_mlp_multi(&fv, 1, st));
+    HIP_TRY(h, launch_marl_rollout(a, 1, st));
+    return CH_OK;
+}
+
+}  // extern "C"

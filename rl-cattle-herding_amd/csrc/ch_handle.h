@@ -1,0 +1,115 @@
+// ch_handle.h — the handle behind the C ABI, private to its two host files: ch_api.cpp (config, create / destroy, reset,
+// step, state, metrics, host output) and ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "ch_internal.h"
+
+// ch_rollout_collect's state (ch_api_policy.cpp)
+struct ch_rollout_state {
+    // the deferred-bootstrap queue (allocated on first use, grown when a call needs more): terminal observations,
+    // their rewards rows, the count, the values; and the bytes each buffer holds
+    float* tv_obs = nullptr;
+    long long* tv_row = nullptr;
+    int* tv_count = nullptr;
+    float* tv_val = nullptr;
+    size_t tv_obs_bytes = 0, tv_row_bytes = 0, tv_count_bytes = 0, tv_val_bytes = 0;
+    // the collection's path (diagnostics / tests, ch__set_rollout_path): bit 0 copy every step's observation into
+    // the buffer instead of stepping into its slots, bit 1 the stand-alone store kernel instead of the forward epilogues,
+    // bit 2 the actor forward fused into the step kernel (k_step2_actor, where the geometry takes it), bit 3 never fused
+    int path = 0;
+    long long fused_steps = 0;   // fused steps launched by ch_rollout_collect (ch__rollout_fused_steps)
+};
+
+// ch_outputs_to_host's device staging of the envs that auto-reset (allocated on first use): count, indices,
+// episode statistics, terminal observation blocks; and the pinned host copy of the count
+struct ch_staging {
+    long long* count = nullptr;
+    long long* env = nullptr;
+    double* stats = nullptr;
+    float* obs = nullptr;
+    long long* count_host = nullptr;
+    // how many ended envs ch_outputs_to_host copies before it knows the count: twice the larger of the last count and
+    // its running mean, plus 8 (a step where more end costs one more copy and stream sync)
+    double ended_mean = 8.0;
+    int64_t ended_last = 8;
+};
+
+struct ch_handle {
+    ch_config cfg{};
+    int64_t E = 0;
+    int device = 0;
+    int NC = 0, M = 0, rows = 0, K = 0, team = 0;
+    int start_level = 0;
+    double episode_len = 0;
+    size_t rsize = 8;
+    void* drone = nullptr;
+    // Euler angles of each drone's stored quaternion, written by the v2 step at the end of every
+    // step (it needs them for the observation anyway) and read by the next one instead of
+    // recomputing atan2/asin/atan2; any other writer of the state clears rpy_valid.
+    void* rpy = nullptr;
+    uint8_t* stale = nullptr;   // device [2][E]: StepParams::stale (Euler cache stale, obs bytes unknown, per env)
+    unsigned long long* obs_tag = nullptr;   // device [E]: StepParams::obs_tag (the buffer holding env e's constant obs bytes)
+    void* cattle = nullptr;
+    void* phys = nullptr;   // [kPhysComps][E][NC]: last_clipped_action, DYN rpy_rates
+    void* envr = nullptr;
+    // f32 mode only: the f64 copies of the positions and prev_cent_dists the step integrates and measures
+    // centroids on (StepParams::pos64 / cpos64 / prev64); the f32 arrays above keep their rounded values
+    double* pos64 = nullptr;    // [3][E][NC]
+    double* cpos64 = nullptr;   // [2][E][M]
+    double* prev64 = nullptr;   // [E]
+    int* envi = nullptr;
+    double* metrics = nullptr;
+    double* spawn = nullptr;
+    int n_scen = 0, n_cows = 0;
+    double* debug = nullptr;
+    int phase_mask = 0;
+    // The obs buffer whose constant-zero bytes (rows >= NUM_DRONES, the action-buffer block, padding)
+    // are known to hold zeros: the last one a full-block writer (v1 step, full ch_reset, v2 step with
+    // obs_full) wrote.  The v2 step then stores only the entries that change.
+    const float* obs_zero_ptr = nullptr;
+    // v2 step kernel (ch_step.hip): envs per workgroup, block size, dynamic LDS, cow-pair list
+    int kernel = 2;
+    long long* tstamp = nullptr;
+    int G = 1, block = 64, P = 0;
+    bool pw = false;   // v2 with per-wave env tables (herds of kPwMinCattle cows and more)
+    bool sep = false;  // v2 shared tables with the shepherd terms in their own LDS region
+    size_t lds = 0;
+    uint16_t* pairs = nullptr;
+    int* errw = nullptr;        // device error word (CH_DEVERR_* bits), sticky
+    double* evald = nullptr;    // [E][NC] evaluation distances (cfg.eval_metrics)
+    int* rdn = nullptr;         // ch_reset_with: device copies of the injected draws
+    double* rdv = nullptr;
+    double* mdev = nullptr;     // device [CH_METRIC_COUNT + 1]: reduced metrics + error word
+    double* mhost = nullptr;    // pinned host copy of mdev
+    long long multi_steps = 0;   // steps ch_step_n ran inside k_step2_multi (ch__multi_steps)
+    void* d_params = nullptr;    // k_step2_multi's parameters (device copy, ch_step_n)
+    std::vector<unsigned char> params_host;   // what d_params holds (uploaded again only when the parameters change)
+    ch_rollout_state ro;
+    ch_staging st;
+    // the device error word was reported to the caller (device_status) since it was last cleared
+    bool err_seen = false;
+    std::string err;
+};
+
+// the message ch_last_error(NULL) returns: failures without a handle, from either host file (defined in ch_api.cpp)
+extern thread_local std::string g_create_err;
+
+inline int fail(ch_handle* h, int code, const std::string& msg) {
+    if (h) h->err = msg; else g_create_err = msg;
+    return code;
+}
+
+#define HIP_TRY(h, expr)                                                                           \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess)                                                                      \
+            return fail((h), CH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));   \
+    } while (0)
+
+// ch_rollout_collect's fused step (ch_api.cpp; launch_step_v2_actor): the step of `io` with the actor forward `fa` on
+// the observations it writes (fa.x == io->obs) and the sampling epilogue `ro`.  launch = false: hipSuccess iff the
+// handle and the net fit the fused kernel (nothing launched).
+hipError_t step_actor(ch_handle* h, const ch_step_io* io, hipStream_t st, const ch::MlpArgs& fa, const ch::RolloutArgs& ro,
+                      bool launch);

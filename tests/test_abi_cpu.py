@@ -104,3 +104,22 @@ def test_mlp_packed_size_is_the_operand_layout():
     assert L.ch_mlp_packed_size(ctypes.byref(net)) == want
     net.dims[1] = 300
     assert L.ch_mlp_packed_size(ctypes.byref(net)) == -1
+
+
+def test_null_handle_errors_share_one_message_across_host_files():
+    """The forwards and the rollout collection live in another translation unit than ch_last_error: a failure
+    without a handle in either is what ch_last_error(NULL) reports next (no device needed: rejected on entry)."""
+    from cattleherd import _lib
+    from cattleherd.rollout import _bind
+    L = _bind()
+    c = _lib.ChConfig()
+    c.physics = 7
+    h = ctypes.c_void_p()
+    assert L.ch_create(ctypes.byref(c), 8, 0, ctypes.byref(h)) == _lib.CH_ERR_INVALID
+    assert b"ch_create" in L.ch_last_error(None)
+    assert L.ch_mlp_forward(None, None, 0, None, None) == _lib.CH_ERR_INVALID
+    assert L.ch_last_error(None).startswith(b"ch_mlp_forward: ")
+    assert L.ch_rollout_collect(None, None, None, None, None, None, 0, 0.99, 0.95, 1, None) == _lib.CH_ERR_INVALID
+    assert L.ch_last_error(None).startswith(b"ch_rollout_collect: ")
+    assert L.ch_default_config(None, 0, 4, 16) == _lib.CH_ERR_INVALID   # and back in the first file
+    assert L.ch_last_error(None).startswith(b"ch_default_config: ")

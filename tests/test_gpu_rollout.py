@@ -104,7 +104,7 @@ def test_rollout_buffer_matches_sb3_semantics(E, n, m, compat, level):
 def test_native_collect_equals_python_loop(T, path):
     """ch_rollout_collect (the loop in C++) and collect_steps (the same kernels launched from Python) fill
     identical buffers, across auto-resets and truncation bootstraps: rollouts shorter than the deferred bootstrap's
-    16-step flush period (kTvEvery, ch_api.cpp), crossing it, and ending exactly on a flush (16, 32), on each of the
+    16-step flush period (kTvEvery, ch_api_policy.cpp), crossing it, and ending exactly on a flush (16, 32), on each of the
     collection's paths (the store folded into the
     forward epilogues, the stand-alone store kernel, every observation copied into the buffer)."""
     import ctypes
@@ -126,6 +126,77 @@ def test_native_collect_equals_python_loop(T, path):
         rb = DeviceRolloutBuffer(b, T)
         log_std = torch.full((4 * n,), -1.0, device=b.device)
         (rb.collect if native else rb.collect_steps)(actor, critic, log_std, seed=9)
+        torch.cuda.synchronize()
+        bufs.append({k: getattr(rb, k).cpu() for k in ("obs", "actions", "rewards", "episode_starts", "values",
+                                                        "log_probs", "advantages", "returns")})
+        assert rb.episode_starts[1:].sum() > 0
+        b.close()
+    for k in bufs[0]:
+        assert torch.equal(bufs[0][k], bufs[1][k]), k
+
+
+@pytest.mark.parametrize("T", [5, 17])
+@pytest.mark.parametrize("path", [0, 2], ids=["epilogues", "store_kernel"])
+def test_native_collect_without_bootstrap(T, path):
+    """bootstrap_truncated = False: no terminal values, no queue, and on the store-kernel path no post launch after
+    the last step -- the GAE kernel runs that post itself.  ch_rollout_collect and collect_steps fill identical
+    buffers, across auto-resets and truncations at every step of the rollout."""
+    import ctypes
+    import torch
+    from cattleherd import _lib
+    from cattleherd.env import HerdBatch
+    from cattleherd.policy import DevicePolicy
+    from cattleherd.rollout import DeviceRolloutBuffer
+    E, n, m = 64, 4, 16
+    sc = 4800 - T // 2 + (np.arange(E) % T)   # truncations at every step of the rollout
+    bufs = []
+    for native in (True, False):
+        b = HerdBatch(E, n, m, mode="ctde", curriculum_level=2)
+        b.reset()
+        b.set_state({"step_counter": sc})
+        assert _lib.lib().ch__set_rollout_path(b.handle, ctypes.c_int32(path)) == 0
+        actor = DevicePolicy(DevicePolicy.random_layers([12 * 86, 128, 128, 4 * n], seed=1), "tanh", None)
+        critic = DevicePolicy(DevicePolicy.random_layers([12 * 86, 128, 128, 1], seed=2), "tanh", None)
+        rb = DeviceRolloutBuffer(b, T)
+        log_std = torch.full((4 * n,), -1.0, device=b.device)
+        (rb.collect if native else rb.collect_steps)(actor, critic, log_std, seed=9, bootstrap_truncated=False)
+        torch.cuda.synchronize()
+        bufs.append({k: getattr(rb, k).cpu() for k in ("obs", "actions", "rewards", "episode_starts", "values",
+                                                        "log_probs", "advantages", "returns")})
+        assert rb.episode_starts[1:].sum() > 0
+        b.close()
+    for k in bufs[0]:
+        assert torch.equal(bufs[0][k], bufs[1][k]), k
+
+
+def test_fused_net_on_the_store_kernel_path():
+    """One fused actor-critic net with the stand-alone store kernel (path bit 1) against the separate actor and
+    critic on the same path: bit-identical buffers, across auto-resets and a flush of the deferred bootstrap."""
+    import ctypes
+    import torch
+    from cattleherd import _lib
+    from cattleherd.env import HerdBatch
+    from cattleherd.policy import DevicePolicy
+    from cattleherd.rollout import DeviceRolloutBuffer
+    from helpers import load
+    d = load("policy_ctde_v16_6.npz")
+    sd = {k.replace("__", "."): torch.tensor(d[k]) for k in d.files if "__" in k}
+    actor, critic = DevicePolicy.sb3_actor(sd, clip=False), DevicePolicy.sb3_critic(sd)
+    fused = DevicePolicy.sb3_actor_critic(sd)
+    E, T, n, m = 64, 17, 4, 16
+    sc = 4800 - T // 2 + (np.arange(E) % T)
+    bufs = []
+    for use_fused in (False, True):
+        b = HerdBatch(E, n, m, mode="ctde", curriculum_level=7)
+        b.reset()
+        b.set_state({"step_counter": sc})
+        assert _lib.lib().ch__set_rollout_path(b.handle, ctypes.c_int32(2)) == 0
+        rb = DeviceRolloutBuffer(b, T, act_dim=48)
+        log_std = torch.full((48,), -1.0, device=b.device)
+        if use_fused:
+            rb.collect(fused, None, log_std, seed=4)
+        else:
+            rb.collect(actor, critic, log_std, seed=4)
         torch.cuda.synchronize()
         bufs.append({k: getattr(rb, k).cpu() for k in ("obs", "actions", "rewards", "episode_starts", "values",
                                                         "log_probs", "advantages", "returns")})

@@ -172,6 +172,54 @@ def test_handoff_timeout_is_reported_not_silent():
         h.close()
 
 
+def test_step_io_validation_is_shared():
+    """ch_step and ch_step_n reject a bad io with CH_ERR_INVALID before any launch, through one validation: after the
+    function's own prefix the messages are the same text, no multi-step launch is counted, and the next valid step
+    is the only one the metrics see."""
+    from cattleherd import _lib
+    from cattleherd.env import HerdBatch
+    L = _lib.lib()
+    E = 4
+    b = HerdBatch(E, 2, 8, mode="ctde")
+    b.reset()
+    b.metrics(reset=True)
+    good = _lib.ChStepIO.from_buffer_copy(b._io)
+    good.actions, good.actions_out = b.actions.data_ptr(), None
+    good.terminal_obs = b.terminal_obs.data_ptr()
+    good.flags = _lib.CH_STEP_AUTORESET
+
+    def variant(**kw):
+        io = _lib.ChStepIO.from_buffer_copy(good)
+        for k, v in kw.items():
+            setattr(io, k, v)
+        return ctypes.byref(io)
+    cases = {"io NULL": None,
+             "obs NULL": variant(obs=None),
+             "actions NULL": variant(actions=None),
+             "actions misaligned": variant(actions=b.actions.data_ptr() + 4),
+             "obs misaligned": variant(obs=b.obs.data_ptr() + 4),
+             "terminal_obs misaligned": variant(terminal_obs=b.terminal_obs.data_ptr() + 4)}
+    m0 = L.ch__multi_steps(b.handle)
+    texts = set()
+    for what, io in cases.items():
+        msgs = []
+        for who, call in (("ch_step", lambda: L.ch_step(b.handle, io, b._stream())),
+                          ("ch_step_n", lambda: L.ch_step_n(b.handle, io, 3, b._stream()))):
+            assert call() == _lib.CH_ERR_INVALID, (what, who)
+            msg = L.ch_last_error(b.handle).decode()
+            assert msg.startswith(who + ": "), (what, msg)
+            msgs.append(msg[len(who) + 2:])
+        assert msgs[0] == msgs[1] and msgs[0], (what, msgs)
+        texts.add(msgs[0])
+    assert len(texts) == 5   # the two obs buffers share the alignment message; every other failure has its own
+    assert L.ch_step_n(b.handle, ctypes.byref(good), 0, b._stream()) == _lib.CH_ERR_INVALID
+    assert "n_steps" in L.ch_last_error(b.handle).decode()
+    assert L.ch__multi_steps(b.handle) == m0
+    assert L.ch_step(b.handle, ctypes.byref(good), b._stream()) == _lib.CH_OK
+    assert b.metrics()[_lib.METRIC_NAMES.index("steps")] == E
+    b.close()
+
+
 def test_step_n_under_graph_capture():
     """ch_step_n inside a HIP graph capture records plain ch_step launches (no multi-step launch, no parameter
     upload in the graph): two replays equal 2 x K ch_step calls bit for bit, also after a ch_step_n of other io
