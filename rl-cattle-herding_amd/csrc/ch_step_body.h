@@ -157,12 +157,22 @@ __device__ __forceinline__ void cow_sync(int* f, int waves, bool global, int* er
 // 3 after the first barrier, 4 drone chain done, 5 reward terms done, 6 herded flags received,
 // 7 bookkeeping done, 8 cow waves: alpha rows done, 9 drone positions received, 10 velocity update
 // done, 11 obs copy done, 12 CU id, 13 second barrier, 14 end)
-#define TS(slot, val) do { if (p.tstamp) p.tstamp[(long long)blockIdx.x * 128 + (slot)] = (val); } while (0)
+#define TS(slot, val) do { if (!PIPE && p.tstamp) p.tstamp[(long long)blockIdx.x * 128 + (slot)] = (val); } while (0)
 // diagnostics: per cow wave 1..6, chunks taken and cycles spent in each dynamic loop (slots 64 + 10 (w - 1) + 2 loop)
-#define CHUNK_T0 const long long ck0_ = p.tstamp ? (long long)clock64() : 0
+#define CHUNK_T0 const long long ck0_ = (!PIPE && p.tstamp) ? (long long)clock64() : 0
 // diagnostics: the latest of the cow waves at a point (per-workgroup max of the shader clock in slot `slot`)
-#define TS_MAX(slot) do { if (p.tstamp && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.tstamp + (long long)blockIdx.x * 128 + (slot)), (unsigned long long)clock64()); } while (0)
-#define CHUNK_T1(loop) do { if (p.tstamp && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) <= 6) { long long* q_ = p.tstamp + (long long)blockIdx.x * 128 + 64 + 10 * ((threadIdx.x >> 6) - 1) + 2 * (loop); q_[0] += 1; q_[1] += (long long)clock64() - ck0_; } } while (0)
+#define TS_MAX(slot) do { if (!PIPE && p.tstamp && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.tstamp + (long long)blockIdx.x * 128 + (slot)), (unsigned long long)clock64()); } while (0)
+#define CHUNK_T1(loop) do { if (!PIPE && p.tstamp && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) <= 6) { long long* q_ = p.tstamp + (long long)blockIdx.x * 128 + 64 + 10 * ((threadIdx.x >> 6) - 1) + 2 * (loop); q_[0] += 1; q_[1] += (long long)clock64() - ck0_; } } while (0)
+
+// (step2_body's PIPE instantiations write none of the slots above: its waves are in different steps at once.)  The
+// pipelined step loop's own stamps, 16 slots per step for the first 8 steps of a launch (slot 16 k + i), shader clock:
+//   drone wave of step k: 0 at the P_N wait (step 0: launch start), 1 chain start, 2 D published, 3 H received,
+//   4 R published, 5 P_N signalled, 6 books written back (P_B), 7 HW_ID
+//   cow waves: 8 first cow wave enters step k (at the P_B wait), 9 past P_B and P_C, 10 waits for D, 11 D seen,
+//   12 flock work done, waits for R (first cow wave), 13 the same, latest cow wave, 14 R seen (first cow wave),
+//   15 step end, latest cow wave
+#define PTS(i, val) do { if (PIPE && p.tstamp && kstep < 8) p.tstamp[(long long)blockIdx.x * 128 + 16 * kstep + (i)] = (val); } while (0)
+#define PTS_MAX(i) do { if (PIPE && p.tstamp && kstep < 8 && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.tstamp + (long long)blockIdx.x * 128 + 16 * kstep + (i)), (unsigned long long)clock64()); } while (0)
 
 template <class R>
 struct V2Smem {
@@ -757,6 +767,30 @@ __device__ __forceinline__ void flock_combine(const StepParams<R>& p, V2Smem<R>&
     velocity_update(p, S, M, e0, u, ddx, ddy);
 }
 
+// LDS of the pipelined step loop (k_step2_multi, configs[3] f64), placed after the V2Layout carve:
+//   ho   [27][64]  per drone lane: the 26 state reals after the chain (a reset env: its new body) and evald's accumulator
+//   hoi  [2][64]   NUM_DRONES of the lane's env for the next step, the Philox step counter
+//   d1   [7][64]   the odd steps' copy of S.dx, dy, dz, dq (the even steps use the V2Layout arrays)
+//   flags1 [kV2Flags]  the odd steps' hand-off and work counters (the even steps: S.flags)
+//   sync           counters that run over the whole launch, never cleared inside it:
+//       P_N  = steps whose hand-off is final       (drone wave k -> drone wave k+1; target k+1)
+//       P_B  = steps whose books are written back  (drone wave k -> cow waves; target k+1)
+//       P_C  = cow waves done with a step, summed  (cow waves among themselves; target W1 (k+1))
+//       P_SIMD + w = 1 + the SIMD of drone wave w
+// Invariant: step k uses counter set k & 1; that set is zero when step k's first signal can arrive (step 0 and 1: cleared
+// before the launch's only barrier; step k >= 2: cleared by the cow waves on entering step k-1, see phase 0).
+template <class R>
+struct V2Pipe {
+    enum { P_N = 0, P_B, P_C, P_SIMD, P_COUNT = 8 };
+    static constexpr size_t kBytes = (27 + 7) * 64 * sizeof(R) + (2 * 64 + kV2Flags + P_COUNT) * sizeof(int);
+    R *ho, *d1;
+    int *hoi, *flags1, *sync;
+    __device__ explicit V2Pipe(unsigned char* base) {
+        ho = (R*)base; d1 = ho + 27 * 64;
+        hoi = (int*)(d1 + 7 * 64); flags1 = hoi + 2 * 64; sync = flags1 + kV2Flags;
+    }
+};
+
 // GT/NT/MT > 0 specialise the kernel for one geometry (envs per workgroup, drones, cattle): the LDS
 // carve and all index arithmetic then fold to immediates, which keeps the kernel within the SGPR file.
 // TOBS: the instantiation that writes terminal observations from their producers in the fast path (configs[3]'s
@@ -766,10 +800,18 @@ __device__ __forceinline__ void flock_combine(const StepParams<R>& p, V2Smem<R>&
 // salt: 0.  k_step2_multi passes an opaque 0 per step (an empty asm's output), so that the values derived from the
 // thread / workgroup indices and the LDS carve are computed inside each step instead of being hoisted out of its step
 // loop and held across it (which overflowed the registers); k_step2's constant 0 folds away.
-template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, bool TOBS>
-__device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0) {
+//
+// ROLE / kstep (k_step2_multi's pipelined instantiation, configs[3] f64; ROLE 0 everywhere else): the workgroup has two
+// drone waves (waves 0 and 1) that alternate steps and its cow waves start at wave 2.  A call runs one role of step
+// `kstep` of the launch: ROLE 1 the drone wave's part (chain, books), ROLE 2 the cow waves' part.  No workgroup barrier
+// separates two steps; the syncs that replace it are the V2Pipe counters (see there).
+template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, bool TOBS, int ROLE = 0>
+__device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0, int kstep = 0) {
     extern __shared__ __align__(16) unsigned char smem_[];
     unsigned char* const smem = smem_ + salt;
+    constexpr bool PIPE = ROLE != 0;
+    static_assert(!PIPE || (sizeof(R) == 8 && MODE == 0 && GT == 16 && NT == 4 && !PW && !TOBS && !PHYS),
+                  "the pipelined step loop is the configs[3] f64 instantiation's");
     constexpr bool marl = MODE == 1;
     // f32 mode: positions, centroids and the approach delta in f64 (StepParams::pos64); PT = their type
     constexpr bool MIX = sizeof(R) == 4;
@@ -787,7 +829,22 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
     const V2Layout L(G, N, M, P, MODE, (int)sizeof(R), PW ? (int)(blockDim.x >> 6) - 1 : 0, !PW && p.sep);
     const bool sep = L.sep;
     V2Smem<R> S(smem, L);
-    const int BS = blockDim.x + salt, tid = threadIdx.x + salt;
+    // PIPE: the drone wave's lanes are 0..63 whichever of the two waves runs the step, and the cow waves count from
+    // 64 as in a workgroup with one drone wave (so ct, CW and W1 below hold)
+    const int BS = (PIPE ? (int)blockDim.x - 64 : (int)blockDim.x) + salt;
+    const int tid = (ROLE == 1 ? (int)(threadIdx.x & 63) : ROLE == 2 ? (int)threadIdx.x - 64 : (int)threadIdx.x) + salt;
+    const bool isd = ROLE == 1 ? true : ROLE == 2 ? false : tid < 64;   // this wave is the step's drone wave
+    const V2Pipe<R> X(smem + (PIPE ? L.bytes() : 0));
+    int* const ps = X.sync;
+    int* const flags0 = S.flags;   // the even steps' counter set
+    if constexpr (PIPE) {
+        // the step's copy of the arrays the cow waves read from the drone wave, and its set of hand-off counters
+        if (kstep & 1) {
+            S.dx = X.d1; S.dy = S.dx + G * N; S.dz = S.dy + G * N; S.dq = S.dz + G * N;
+            S.dxd = (double*)S.dx; S.dyd = (double*)S.dy;
+            S.flags = X.flags1;
+        }
+    }
     const int e0 = (blockIdx.x + salt) * G;
     const int Gv = min(G, p.E - e0);
     const long long E = p.E, DS = E * N, CS = E * M;
@@ -799,7 +856,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
     int* fl = S.flags;
     const Level* LT = S.LT;
     if (tid == 0) { TS(0, (long long)wall_clock64()); TS(2, (long long)clock64()); TS(12, (long long)__smid()); }
-    if ((tid & 63) == 0 && tid < 256) TS(22 + (tid >> 6), (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));   // HW_ID
+    if ((tid & 63) == 0 && tid < 256 && !PIPE) TS(22 + (tid >> 6), (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));   // HW_ID
 
     // ---- phase 0: env scalars, drone prefetch (wave 0); cattle integration, image zero-fill (cow waves).
     // Every wave issues its global loads before the first barrier, so their latency overlaps the launch of
@@ -827,7 +884,34 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
     double pd[3] = {0, 0, 0};   // MIX: f64 drone position
     uint8_t stale_o = 0;        // cow waves' env lanes: the obs block flag and the buffer tag, combined after the barrier
     unsigned long long tag_o = 0;
-    if (tid >= 64) {
+    if constexpr (PIPE) {
+        if (ROLE == 1 && tid == 0) { PTS(0, (long long)clock64()); PTS(7, (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4)); }
+        if (ROLE == 2 && ct == 0) PTS(8, (long long)clock64());
+        if (kstep > 0) {
+            if (ROLE == 2) {
+                // (a) step k's loads come after step k-1's stores: the books wave's write-back (P_B, released at
+                // workgroup scope by that wave) and every cow wave's final pass (P_C, a cow-wave barrier that publishes
+                // their global stores).  (c) the outputs of step k are ordered after those of step k-1 through the
+                // same chain: the books of step k wait for this step's cow items (F_H).
+                lds_wait(ps + V2Pipe<R>::P_B, kstep, p.err);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                lds_signal(ps + V2Pipe<R>::P_C);
+                lds_wait(ps + V2Pipe<R>::P_C, W1 * kstep, p.err);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                // (b) the counters of step k-1 are cleared for step k+1 once every wave is done with them: the cow
+                // waves by P_C, the books wave by P_B.  Step k+1's drone wave touches them only after R_k, which
+                // follows this step's F_E and F_H, which follow this clear.
+                int* const flp = (kstep & 1) ? flags0 : X.flags1;
+                if (ct < kV2Flags) flp[ct] = 0;
+            } else {
+                // the chain state of step k-1 (and, for its reset envs, the new bodies): final
+                lds_wait(ps + V2Pipe<R>::P_N, kstep, p.err);
+            }
+        }
+        if (ROLE == 1 && tid == 0) PTS(1, (long long)clock64());
+        if (ROLE == 2 && ct == 0) PTS(9, (long long)clock64());
+    }
+    if (!isd) {
         if (ct < Gv * M) {
             const long long ci = (long long)e0 * M + ct;
 #pragma unroll
@@ -846,6 +930,21 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
 #pragma unroll
             for (int r = 0; r < kMetricRows; ++r) met0[r] = p.metrics[r * E + e];
         }
+    } else if (PIPE && kstep > 0) {
+        // the chain state from the previous step's drone wave, through LDS (global memory holds the same values)
+        const R* ho = X.ho + tid;
+        pos[0] = ho[0 * 64]; pos[1] = ho[1 * 64]; pos[2] = ho[2 * 64];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) q[c] = ho[(3 + c) * 64];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { v[c] = ho[(7 + c) * 64]; w[c] = ho[(10 + c) * 64]; }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) pid[c] = ho[(13 + c) * 64];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ql[c] = ho[(22 + c) * 64];
+        ev_acc = ho[26 * 64];
+        n0 = X.hoi[tid]; stepi = X.hoi[64 + tid];
+        stale_d = 1;   // the Euler angles of this attitude are computed here (the cow waves' pass stores the cache later)
     } else if (dlane) {
         // the drone wave loads only what its chain reads, so the chain starts after one round trip; the
         // cow waves stage the env scalars, the curriculum table and the pair list meanwhile
@@ -878,14 +977,16 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
             for (int c = 0; c < 3; ++c) ph_rr[c] = p.phys[(4 + c) * DS + di];
         }
     }
+    if constexpr (!PIPE) {
     if (tid < Gv) stepi_env = p.envi[9 * E + e0 + tid];   // env lanes: the counter the write-back advances
     if (tid < kV2Flags) fl[tid] = 0;
     if constexpr (PW) { if (tid < G) reinterpret_cast<int*>(S.hasnb)[tid] = 0; }   // per-env alpha-row ready flags
     lds_barrier();   // hand-off counters cleared before anyone signals
+    }
 
-    if (tid < 64) {
+    if (isd) {
         __builtin_amdgcn_s_setprio(3);   // the drone wave is the critical path: it wins issue on a shared SIMD
-        if (tid == 0)
+        if (tid == 0 && !PIPE)
             __hip_atomic_store(fl + V_DSIMD, 1 + (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_WORKGROUP);
     } else {
@@ -946,9 +1047,10 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
         }
         cow_sync(fl + F_E, W1, false, p.err);   // env scalars, flocking list, tables: seen by every cow wave
         {
-            int ds = lds_peek(fl + V_DSIMD);
+            // PIPE: the SIMD of the wave that runs this step's chain (stored once per launch, step2_pipe_init)
+            int ds = PIPE ? ps[V2Pipe<R>::P_SIMD + (kstep & 1)] : lds_peek(fl + V_DSIMD);
             int spins = 0;
-            for (; ds == 0 && spins < (1 << 22); ++spins) {   // stored by the drone wave at its start
+            for (; ds == 0 && spins < (1 << 22) && !PIPE; ++spins) {   // stored by the drone wave at its start
                 __builtin_amdgcn_s_sleep(1);
                 ds = lds_peek(fl + V_DSIMD);
             }
@@ -1004,7 +1106,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
     PT f_prev = 0;   // prev_cent_dists (f64 also in f32 mode: the approach delta is a difference of two ~10 m distances)
     R f_clock = 0;
 
-    if (tid < 64) {
+    if (isd) {
         // ============ drone wave: the critical path ============================================
         const int n = dlane ? n0 : 0;
         const bool live = dlane && dk < n;
@@ -1070,11 +1172,34 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
         }
         wave_sync();
         lds_signal(fl + F_D);   // positions published: the cow waves' distance work starts now
+        if constexpr (PIPE) {
+            // the chain state for the next step's drone wave (every lane its own slots; a reset env's are rewritten
+            // below, before P_N)
+            R* ho = X.ho + tid;
+            ho[0 * 64] = pos[0]; ho[1 * 64] = pos[1]; ho[2 * 64] = pos[2];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) ho[(3 + c) * 64] = q[c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { ho[(7 + c) * 64] = v[c]; ho[(10 + c) * 64] = w[c]; }
+#pragma unroll
+            for (int c = 0; c < 9; ++c) ho[(13 + c) * 64] = pid[c];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) ho[(22 + c) * 64] = ql[c];
+            X.hoi[tid] = n0; X.hoi[64 + tid] = stepi + 1;
+        }
         // the own-state row but its Euler angles, which a cow wave computes from S.dq (obs_euler)
         if (live && wobs) obs_own_nrpy(obs_wg + dg * RW, dk, pos[2], v, w);
-        if (tid == 0) TS(4, (long long)clock64());
+        if (tid == 0) { TS(4, (long long)clock64()); PTS(2, (long long)clock64()); }
+        // (PIPE: the cow waves enter this step only after the previous step's books, so this wait can be a real one:
+        // not at raised priority)
+        if constexpr (PIPE) __builtin_amdgcn_s_setprio(0);
         lds_wait(fl + F_E, W1, p.err);   // env scalars and the curriculum table (staged by the cow waves)
-        if (p.evald && live) CH_STS(&p.evald[di], eval_distance_step(ev_acc, ei[I_SC * G + dg] == 0, px0, py0, pos[0], pos[1]));
+        if constexpr (PIPE) __builtin_amdgcn_s_setprio(3);
+        if (p.evald && live) {
+            ev_acc = eval_distance_step(ev_acc, ei[I_SC * G + dg] == 0, px0, py0, pos[0], pos[1]);
+            CH_STS(&p.evald[di], ev_acc);
+        }
+        if constexpr (PIPE) X.ho[26 * 64 + tid] = ev_acc;
 
         // per-drone reward terms (CattleAviary.py:230-246, 572-679) and neighbour obs (BaseRLAviary.py:303-317)
         int nb1 = -1, nb2 = -1;   // the two nearest drones (kept for a fast reset's terminal observation)
@@ -1127,7 +1252,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
         const bool envl = QUAD ? dlane : g < Gv;
         const bool envw = envl && (!QUAD || dk == 0);
         lds_wait(fl + F_H, Gv * M + force, p.err);   // every cow item
-        if (tid == 0) TS(6, (long long)clock64());
+        if (tid == 0) { TS(6, (long long)clock64()); PTS(3, (long long)clock64()); }
         if (live && task) {
             if constexpr (QUAD) q_sc = cattle_term(S, tid, M, R(p.cs_cc));
             else S.scat[tid] = cattle_term(S, tid, M, R(p.cs_cc));
@@ -1451,7 +1576,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
         if (tid == 0) TS(27, (long long)clock64());
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         lds_signal(fl + F_R);
-        if (tid == 0) TS(15, (long long)clock64());
+        if (tid == 0) { TS(15, (long long)clock64()); PTS(4, (long long)clock64()); }
         if (fast && ei[NR_AT]) {
             // SB3 auto-reset, drone side (BaseAviary.reset, BaseAviary.py:280-331): each drone lane of a reset env
             // writes its new body, Euler cache and observation row itself (it wrote the old ones)
@@ -1473,6 +1598,21 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
             const R z = R(zd);
             wave_sync();   // the env's new drone positions (nearest neighbours)
             if (rd) {
+                if constexpr (PIPE) {
+                    // the new episode's body for the next step's chain: what reset_drone_store leaves in global memory
+                    R* ho = X.ho + tid;
+                    ho[0 * 64] = R(xd); ho[1 * 64] = R(yd); ho[2 * 64] = R(zd);
+                    ho[3 * 64] = 0; ho[4 * 64] = 0; ho[5 * 64] = 0; ho[6 * 64] = 1;
+#pragma unroll
+                    for (int c = 7; c < 13; ++c) ho[c * 64] = 0;
+                    if (!p.compat) {
+#pragma unroll
+                        for (int c = 13; c < 22; ++c) ho[c * 64] = 0;
+                    }
+                    ho[22 * 64] = 0; ho[23 * 64] = 0; ho[24 * 64] = 0; ho[25 * 64] = 1;
+                    ho[26 * 64] = 0;
+                    X.hoi[tid] = n_new;
+                }
                 reset_drone_store(p, di, xd, yd, zd);
                 if constexpr (PHYS) {   // last_clipped_action, rpy_rates = 0 (_housekeeping, BaseAviary.py:565, 581-582)
 #pragma unroll
@@ -1495,6 +1635,14 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
                     }
                 }
             }
+        }
+        if constexpr (PIPE) {
+            // P_N: the hand-off is final (R_k is known, the reset envs' new bodies are in) -- the other drone wave
+            // starts chain k+1.  A workgroup-scope release: this wave's stores of step k to the drone state and the
+            // observation rows are complete before that wave stores step k+1's to the same addresses.
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            lds_signal(ps + V2Pipe<R>::P_N);
+            if (tid == 0) PTS(5, (long long)clock64());
         }
         if (envl && task) {
             const int n = f_n;
@@ -1587,6 +1735,13 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
             p.stale[e] = 0;
             if (wobs) p.stale[E + e] = 0;
             p.obs_tag[e] = wobs ? (unsigned long long)(uintptr_t)p.obs : 0ull;
+        }
+        if constexpr (PIPE) {
+            // P_B: the books of step k are closed and written back (released at workgroup scope): the cow waves may
+            // load step k+1's env scalars and restage the LDS rows this wave read
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            lds_signal(ps + V2Pipe<R>::P_B);
+            if (tid == 0) PTS(6, (long long)clock64());
         }
     } else {
         // ============ cow waves ================================================================
@@ -1740,9 +1895,9 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
             }
             spin_note(sleeps);
         }
-        if (ct == 0) TS(8, (long long)clock64());
+        if (ct == 0) { TS(8, (long long)clock64()); PTS(10, (long long)clock64()); }
         lds_wait(fl + F_D, 1, p.err);
-        if (ct == 0) TS(9, (long long)clock64());
+        if (ct == 0) { TS(9, (long long)clock64()); PTS(11, (long long)clock64()); }
         skip_now = skip_post;
         for (;;) {   // per cow: distances, winding number, observation entries (the herd centroid is done)
             const int b = grab(fl + C_COWS, 64, skip_post), u = b + lane;
@@ -1926,9 +2081,10 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
         }
         if (lane == 0) TS(40 + (tid >> 6), (long long)clock64());   // this cow wave's flock work done
         TS_MAX(57);
-        if (ct == 0) TS(31, (long long)nf);
+        if (ct == 0) { TS(31, (long long)nf); PTS(12, (long long)clock64()); }
+        PTS_MAX(13);
         lds_wait(fl + F_R, 1, p.err);    // the reset list
-        if (tid == 64) TS(37, (long long)clock64());
+        if (tid == 64) { TS(37, (long long)clock64()); PTS(14, (long long)clock64()); }
         const int nr = ei[NR_AT];
         if (ct == 0) TS(30, (long long)nr);
         if (nr && ct == 0) TS(52, (long long)clock64());
@@ -2071,13 +2227,30 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0)
     }
     if (tid == 0) TS(35, (long long)clock64());
     if (tid == 64) TS(36, (long long)clock64());
-    if (tid >= 64) TS_MAX(63);   // diagnostics: the last cow wave's end
+    if (tid >= 64) { TS_MAX(63); PTS_MAX(15); }   // diagnostics: the last cow wave's end
     // No closing barrier: every wave leaves when its own work is done (the LDS lives until the last one
     // has).  With timestamps on, one barrier marks the workgroup's end for the trace.
     if (p.tstamp) {
-        lds_barrier();
+        if constexpr (!PIPE) lds_barrier();   // (PIPE: the waves are in different steps; no barrier inside the step loop)
         if (tid == 0) { TS(13, (long long)clock64()); TS(14, (long long)clock64()); TS(1, (long long)wall_clock64()); }
     }
+}
+
+
+// Once per launch of the pipelined step loop, by every wave: both counter sets and the launch-long counters cleared, the
+// two drone waves' SIMDs recorded, then the launch's only workgroup barrier.
+template <class R, int MODE, int GT, int NT, int MT>
+__device__ __forceinline__ void step2_pipe_init(const StepParams<R>& p) {
+    extern __shared__ __align__(16) unsigned char smem_[];
+    const V2Layout L(GT, NT, MT, MT * (MT - 1) / 2, MODE, (int)sizeof(R), 0, p.sep != 0);
+    V2Smem<R> S(smem_, L);
+    const V2Pipe<R> X(smem_ + L.bytes());
+    const int t = threadIdx.x;
+    if (t < kV2Flags) { S.flags[t] = 0; X.flags1[t] = 0; }
+    if (t < V2Pipe<R>::P_SIMD) X.sync[t] = 0;
+    if ((t & 63) == 0 && t < 128)
+        X.sync[V2Pipe<R>::P_SIMD + (t >> 6)] = 1 + (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3);
+    lds_barrier();
 }
 
 }  // namespace ch

@@ -19,14 +19,25 @@ namespace ch {
 // uniform (readfirstlane) and read through the constant address space, so every parameter read is a scalar load where
 // the step uses it, as from k_step2's kernel arguments (the address of a by-value kernel argument would be a private
 // copy).
-template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW>
-__device__ __forceinline__ void step2_once(const StepParams<R>* p, int salt) {
+template <class R>
+__device__ __forceinline__ const StepParams<R>& uniform_params(const StepParams<R>* p) {
     const unsigned long long a = (unsigned long long)(uintptr_t)p;
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
     using KP = const __attribute__((address_space(4))) StepParams<R>*;
     const KP kp = (KP)(((unsigned long long)hi << 32) | lo);
-    step2_body<R, MODE, GT, NT, MT, PHYS, PW, false>(*(const StepParams<R>*)kp, salt);
+    return *(const StepParams<R>*)kp;
 }
+template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, int ROLE = 0>
+__device__ __forceinline__ void step2_once(const StepParams<R>* p, int salt, int kstep = 0) {
+    step2_body<R, MODE, GT, NT, MT, PHYS, PW, false, ROLE>(uniform_params(p), salt, kstep);
+}
+
+// The instantiation whose step loop is pipelined over two drone waves (configs[3], f64): step k+1's drone chain needs
+// only the bodies after chain k and step k's reset decision, so a second drone wave starts it as soon as R_k is
+// published, while the first still closes the books of step k (reward, metrics, env write-back) -- see V2Pipe and
+// step2_body's ROLE in ch_step_body.h.
+template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, int WPE>
+constexpr bool kMultiPipelined = sizeof(R) == 8 && MODE == 0 && GT == 16 && NT == 4 && MT == 16 && !PHYS && !PW && WPE == 1;
 // n consecutive steps in one launch (ch_step_n); `pd`: the step's parameters in device memory
 // WPE: the waves per SIMD the registers are allocated for (4: two workgroups per CU, for grids of more workgroups than
 // CUs -- the f32 mode at 262 144 envs: 395.5 vs 294.4 M env-steps/s; at 4096 envs, one workgroup per CU, the register
@@ -38,6 +49,29 @@ template <class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW 
 __global__ __launch_bounds__(PW ? CH_V2_MAX_BLOCK_PW : CH_MULTI_MAX_BLOCK)
 __attribute__((amdgpu_waves_per_eu(WPE)))
 void k_step2_multi(const StepParams<R>* __restrict__ pd, int n_steps) {
+    if constexpr (kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE>) {
+        // Waves 0 and 1 are the drone waves: wave 0 runs the drone role of steps 0, 2, ..., wave 1 of steps 1, 3, ...;
+        // the other waves run the cow role of every step.  One barrier per launch (step2_pipe_init); inside the loops
+        // every sync is a bounded LDS-counter wait, so an expired wait leaves no wave waiting for another.
+        step2_pipe_init<R, MODE, GT, NT, MT>(uniform_params(pd));
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (wave < 2) {
+            for (int k = wave; k < n_steps; k += 2) {
+                int salt = 0;
+                const StepParams<R>* q = pd;
+                asm volatile("" : "+s"(salt), "+s"(q));   // (as below)
+                step2_once<R, MODE, GT, NT, MT, PHYS, PW, 1>(q, salt, k);
+                __builtin_amdgcn_s_setprio(0);   // raised only inside the chain and the books, not while it waits for P_N
+            }
+        } else {
+            for (int k = 0; k < n_steps; ++k) {
+                int salt = 0;
+                const StepParams<R>* q = pd;
+                asm volatile("" : "+s"(salt), "+s"(q));   // (as below)
+                step2_once<R, MODE, GT, NT, MT, PHYS, PW, 2>(q, salt, k);
+            }
+        }
+    } else {
     for (int k = 0; k < n_steps; ++k) {
         int salt = 0;
         const StepParams<R>* q = pd;
@@ -47,6 +81,7 @@ void k_step2_multi(const StepParams<R>* __restrict__ pd, int n_steps) {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         __builtin_amdgcn_s_setprio(0);   // (the drone wave's raised priority)
+    }
     }
 }
 
@@ -63,6 +98,14 @@ static hipError_t launch_v2_multi_kernel(const StepParams<R>& p, const StepParam
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         attr_set.fetch_or(bit, std::memory_order_relaxed);
+    }
+    if constexpr (kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE>) {
+        // two drone waves and at least two cow waves that hold the workgroup's cows (three spawn slots per lane); the
+        // fast reset path (sep); room for the hand-off behind the carve
+        const int blk = block < CH_MULTI_MAX_BLOCK ? block : CH_MULTI_MAX_BLOCK;
+        if (blk < 256 || p.G * p.M > 3 * (blk - 128) || !p.sep || lds + V2Pipe<R>::kBytes > 160 * 1024)
+            return hipErrorNotSupported;
+        lds += V2Pipe<R>::kBytes;
     }
     if (!launch) return hipSuccess;
     dim3 grid((p.E + p.G - 1) / p.G);

@@ -18,6 +18,11 @@ from cattleherd.env import HerdBatch  # noqa: E402
 def trace(mode, E, n, m, prec, G=None, B=None, steps=4, summary=None):
     """Print the phase table of `steps` launches; `summary` (a list) receives one dict per launch with the numbers
     bench.py's latency roofline quotes (drone chain and workgroup cycles)."""
+    if _pipelined(mode, E, n, m, prec) and (G is None or G == 16):
+        # that instantiation's waves are in different steps at once: it has per-step stamps of its own (a library
+        # whose kernel is not pipelined writes none of them and gets the table below)
+        if trace_pipe(mode, E, n, m, prec, G, B, launches=steps, summary=summary):
+            return
     L = _lib.lib()
     b = HerdBatch(E, n, m, mode=mode, precision=prec)
     if G is not None:
@@ -157,7 +162,88 @@ def trace(mode, E, n, m, prec, G=None, B=None, steps=4, summary=None):
     b.close()
 
 
+def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
+    """The pipelined step loop of k_step2_multi (configs[3] f64: two drone waves that alternate steps): ch_step_n
+    launches of 8 steps, stamped per step (ch_step_body.h PTS: slot 16 k + i).  Per step k = 2..7, medians over the
+    workgroups, in cycles: R_{k-1} -> chain start k, the chain, D -> H, H -> R, R -> books written back, the period
+    R_{k-1} -> R_k; when the cow waves enter step k and how long they wait for the books of step k-1, for D_k and R_k."""
+    L = _lib.lib()
+    b = HerdBatch(E, n, m, mode=mode, precision=prec)
+    if G is not None:
+        assert L.ch__set_geometry(b.handle, ctypes.c_int32(G), ctypes.c_int32(B)) == 0
+    g, blk, lds, kv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
+    L.ch__geometry(b.handle, ctypes.byref(g), ctypes.byref(blk), ctypes.byref(lds), ctypes.byref(kv))
+    grid = (E + g.value - 1) // g.value
+    ts = torch.zeros((grid, 128), dtype=torch.int64, device=b.device)
+    b.reset()
+    for _ in range(0 if os.environ.get("CH_TRACE_NOBURN") else 250):
+        b.step(random_actions=True, autoreset=True, terminal_obs=False)
+    L.ch__set_tstamp(b.handle, ctypes.c_void_p(ts.data_ptr()))
+    print(f"== pipelined {prec} {mode} E={E} N={n} M={m} G={g.value} block={blk.value} (multi kernel: at most 512 threads) grid={grid}")
+    q50 = lambda x: float(np.percentile(x, 50))  # noqa: E731
+    for s in range(launches):
+        ts.zero_()
+        torch.cuda.synchronize()
+        b.step_n(8, random_actions=True)
+        torch.cuda.synchronize()
+        t = ts.cpu().numpy().reshape(grid, 8, 16)
+        if not ((t[:, :, 4] > 0).all() and (np.diff(t[:, :, 4], axis=1) > 0).all()):   # R of steps 0..7, in order
+            print("   no per-step stamps: this library's kernel is not the pipelined one")
+            b.close()
+            return False
+        simd = (t[:, :2, 7] >> 4) & 3
+        print(f" launch {s}: drone waves on different SIMDs in {int((simd[:, 0] != simd[:, 1]).sum())} of {grid} workgroups")
+        rows = []
+        for k in range(2, 8):
+            R0, c = t[:, k - 1, 4], t[:, k]
+            r = {"R_to_chain_start": q50(c[:, 1] - R0), "drone_waits_PN": q50(c[:, 1] - c[:, 0]),
+                 "chain": q50(c[:, 2] - c[:, 1]), "D_to_H": q50(c[:, 3] - c[:, 2]), "H_to_R": q50(c[:, 4] - c[:, 3]),
+                 "R_to_PN": q50(c[:, 5] - c[:, 4]), "R_to_books_done": q50(c[:, 6] - c[:, 4]),
+                 "period_R_to_R": q50(c[:, 4] - R0),
+                 "cow_entry_after_R": q50(c[:, 8] - R0), "cow_waits_books": q50(c[:, 9] - c[:, 8]),
+                 "cow_start_after_R": q50(c[:, 9] - R0), "cow_ready_for_D_after_R": q50(c[:, 10] - R0),
+                 "cow_waits_D": q50(c[:, 11] - c[:, 10]), "D_after_R": q50(c[:, 2] - R0),
+                 "cow_flock_done_after_D": q50(c[:, 12] - c[:, 11]), "last_cow_flock_done_after_D": q50(c[:, 13] - c[:, 11]),
+                 "cow_waits_R": q50(c[:, 14] - c[:, 12]), "cow_end_after_R_k": q50(c[:, 15] - c[:, 4]),
+                 "resetting_wgs_prev": int(((c[:, 5] - c[:, 4]) > 400).sum())}
+            rows.append(r)
+            print(f"   step {k}: " + " ".join(f"{a}={v:.0f}" for a, v in r.items()))
+        mean = {a: float(np.mean([r[a] for r in rows])) for a in rows[0]}
+        print("   mean of steps 2..7: " + " ".join(f"{a}={v:.0f}" for a, v in mean.items()))
+        if summary is not None:
+            summary.append({"wg_cycles_q50": mean["period_R_to_R"], "chain_cycles_q50": mean["chain"],
+                            "chain_start": mean["R_to_chain_start"], "chain_done": mean["D_after_R"],
+                            "h_received": mean["D_after_R"] + mean["D_to_H"], "reset_list": mean["period_R_to_R"],
+                            "books_done_after_R": mean["R_to_books_done"], "cow_start_after_R": mean["cow_start_after_R"],
+                            "cow_waits_D": mean["cow_waits_D"], "cow_waits_R": mean["cow_waits_R"],
+                            "origin": "R of the previous step (pipelined loop)"})
+    b.close()
+    return True
+
+
+def _pipelined(mode, E, n, m, prec):
+    return bool(os.environ.get("CH_TRACE_MULTI")) and (mode, n, m, prec) == ("ctde", 4, 16, "f64") and E >= 4096
+
+
 def main():
+    if len(sys.argv) >= 2 and sys.argv[1] == "--json" and _pipelined(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), "f64"):
+        a = sys.argv[2:]
+        rows = []
+        if not trace_pipe(a[0], int(a[1]), int(a[2]), int(a[3]), "f64", launches=8, summary=rows):
+            trace(a[0], int(a[1]), int(a[2]), int(a[3]), "f64", steps=8, summary=rows)
+        out = {k: (float(np.mean([r[k] for r in rows])) if not isinstance(rows[0][k], str) else rows[0][k]) for k in rows[0]}
+        out["launches"] = len(rows)
+        out["chain_over_wg"] = out["chain_cycles_q50"] / out["wg_cycles_q50"]
+        if "drone_wave_end" in out:
+            out["post_chain_cycles"] = out["drone_wave_end"] - out["chain_done"]
+        import json
+        print(json.dumps(out), flush=True)
+        return
+    if len(sys.argv) >= 2 and sys.argv[1] == "--pipe":   # --pipe mode E n m [G B]: the pipelined step loop's per-step timeline
+        a = sys.argv[2:]
+        geom = (int(a[4]), int(a[5])) if len(a) >= 6 else (None, None)
+        trace_pipe(a[0], int(a[1]), int(a[2]), int(a[3]), "f64", *geom)
+        return
     if len(sys.argv) >= 2 and sys.argv[1] == "--json":   # --json mode E n m: 8 launches, then one JSON summary line
         a = sys.argv[2:]
         rows = []
@@ -232,7 +318,10 @@ def back_to_back(mode="ctde", E=4096, n=4, m=16, prec="f64", k=12):
 
 
 if __name__ == "__main__":
-    host_rate()
-    back_to_back()
-    if len(sys.argv) > 1:
+    if len(sys.argv) > 1 and sys.argv[1] == "--pipe":
         main()
+    else:
+        host_rate()
+        back_to_back()
+        if len(sys.argv) > 1:
+            main()
