@@ -424,19 +424,23 @@ int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_ma
     // the step writes its observations straight into the buffer's next slot (a step into a buffer other than the one
     // it wrote last writes every block in full); the last step into the env's own buffer.  No terminal observations:
     // an agent's trajectory ends only where it terminates (no bootstrap), so the reset path needs no copy.
+    // With an odd number of agent rows a slot is 8 bytes off the 16-byte alignment the step and the forwards need:
+    // every step then writes the env's own buffer and the store kernel copies it into the slot (as it does at t = 0).
     ch_step_io s = collect_step_io(sio, io->env_actions);
     s.terminal_obs = nullptr;
     const size_t slot = (size_t)a.rows * 86;
+    const bool in_place = (slot * sizeof(float)) % 16 == 0;
     MlpArgs segs[2];
     for (int32_t t = 0; t < rb->n_steps; ++t) {
-        const float* x = t == 0 ? sio->obs : rb->obs + (size_t)t * slot;
+        const bool own = t == 0 || !in_place;
+        const float* x = own ? sio->obs : rb->obs + (size_t)t * slot;
         segs[0] = fp; segs[1] = fv;
         segs[0].x = segs[1].x = x;
         HIP_TRY(h, launch_mlp_multi(segs, 2, st));
         a.t = t;
-        a.obs_now = t == 0 ? sio->obs : nullptr;
+        a.obs_now = own ? sio->obs : nullptr;
         HIP_TRY(h, launch_marl_rollout(a, 0, st));
-        s.obs = t + 1 < rb->n_steps ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
+        s.obs = (in_place && t + 1 < rb->n_steps) ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
         if ((rc = ch_step(h, &s, stream))) return rc;
     }
     // V(obs after the last step) -> last_values, the last step's post, GAE
