@@ -45,8 +45,18 @@ constexpr bool kMultiPipelined = sizeof(R) == 8 && MODE == 0 && GT == 16 && NT =
 #ifndef CH_MULTI_MAX_BLOCK
 #define CH_MULTI_MAX_BLOCK CH_V2_MAX_BLOCK_PW   // 512 threads: 2 waves per SIMD (A/B)
 #endif
+// The pipelined instantiation's own bound: 2 drone waves + 8 cow waves.  Its step loop compiles to 161 VGPRs and no
+// scratch under this bound too (tools/res_usage.sh), inside the 168 registers of 3 waves per SIMD, and the extra cow
+// waves shorten the cow side, which is that loop's critical path (640 beat 576 beat 512).  The other
+// instantiations take 171 VGPRs, which do not fit 3 waves per SIMD: they keep CH_MULTI_MAX_BLOCK.
+#ifndef CH_MULTI_PIPE_MAX_BLOCK
+#define CH_MULTI_PIPE_MAX_BLOCK 640
+#endif
+template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, int WPE>
+constexpr int kMultiMaxBlock = kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE> ? CH_MULTI_PIPE_MAX_BLOCK
+                               : PW ? CH_V2_MAX_BLOCK_PW : CH_MULTI_MAX_BLOCK;
 template <class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW = false, int WPE = 1>
-__global__ __launch_bounds__(PW ? CH_V2_MAX_BLOCK_PW : CH_MULTI_MAX_BLOCK)
+__global__ __launch_bounds__((kMultiMaxBlock<R, MODE, GT, NT, MT, PHYS, PW, WPE>))
 __attribute__((amdgpu_waves_per_eu(WPE)))
 void k_step2_multi(const StepParams<R>* __restrict__ pd, int n_steps) {
     if constexpr (kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE>) {
@@ -89,6 +99,7 @@ template <class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW 
 static hipError_t launch_v2_multi_kernel(const StepParams<R>& p, const StepParams<R>* pd, int block, size_t lds,
                                          hipStream_t st, int n_steps, bool launch) {
     static std::atomic<unsigned long long> attr_set{0};
+    constexpr int max_block = kMultiMaxBlock<R, MODE, GT, NT, MT, PHYS, PW, WPE>;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -102,16 +113,17 @@ static hipError_t launch_v2_multi_kernel(const StepParams<R>& p, const StepParam
     if constexpr (kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE>) {
         // two drone waves and at least two cow waves that hold the workgroup's cows (three spawn slots per lane); the
         // fast reset path (sep); room for the hand-off behind the carve
-        const int blk = block < CH_MULTI_MAX_BLOCK ? block : CH_MULTI_MAX_BLOCK;
+        const int blk = block < max_block ? block : max_block;
         if (blk < 256 || p.G * p.M > 3 * (blk - 128) || !p.sep || lds + V2Pipe<R>::kBytes > 160 * 1024)
             return hipErrorNotSupported;
         lds += V2Pipe<R>::kBytes;
     }
     if (!launch) return hipSuccess;
     dim3 grid((p.E + p.G - 1) / p.G);
-    // at most 8 waves: the step loop needs the registers of 2 waves per SIMD (at 3 per SIMD, 768 threads, the loop's
-    // longer live ranges spilled); the cow waves share their work out dynamically, so the outputs do not depend on it
-    hipLaunchKernelGGL((k_step2_multi<R, MODE, GT, NT, MT, PHYS, PW, WPE>), grid, dim3(block < (PW ? CH_V2_MAX_BLOCK_PW : CH_MULTI_MAX_BLOCK) ? block : (PW ? CH_V2_MAX_BLOCK_PW : CH_MULTI_MAX_BLOCK)),
+    // The handle's block is clamped to the instantiation's launch bound (kMultiMaxBlock): 8 waves where the step loop
+    // needs the registers of 2 waves per SIMD, 10 for the pipelined instantiation, whose loop fits 3 per SIMD.  The cow
+    // waves share their work out dynamically, so the outputs do not depend on how many of them run.
+    hipLaunchKernelGGL((k_step2_multi<R, MODE, GT, NT, MT, PHYS, PW, WPE>), grid, dim3(block < max_block ? block : max_block),
                        lds, st, pd, n_steps);
     return hipGetLastError();
 }

@@ -179,7 +179,7 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
     for _ in range(0 if os.environ.get("CH_TRACE_NOBURN") else 250):
         b.step(random_actions=True, autoreset=True, terminal_obs=False)
     L.ch__set_tstamp(b.handle, ctypes.c_void_p(ts.data_ptr()))
-    print(f"== pipelined {prec} {mode} E={E} N={n} M={m} G={g.value} block={blk.value} (multi kernel: at most 512 threads) grid={grid}")
+    print(f"== pipelined {prec} {mode} E={E} N={n} M={m} G={g.value} block={blk.value} (clamped to the multi kernel's launch bound) grid={grid}")
     q50 = lambda x: float(np.percentile(x, 50))  # noqa: E731
     for s in range(launches):
         ts.zero_()
