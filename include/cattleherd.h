@@ -405,6 +405,76 @@ typedef struct ch_marl_rollout_io {
 int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
                             const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream);
 
+/* ---- Native PPO minibatch update ---------------------------------------------------------------------------
+ * Replaces: stable_baselines3 PPO.train for the CTDE driver's PPO("MlpPolicy", ...) (CTDECattleHerder.py:107-150),
+ * one minibatch step at a time: ActorCriticPolicy.evaluate_actions (separate tanh MLPs obs -> pi -> action_net and
+ * obs -> vf -> value_net, DiagGaussian with a free log_std), per-minibatch advantage normalisation (torch's unbiased
+ * std, skipped for a one-row minibatch), the clipped surrogate, vf_coef * MSE value loss, the entropy bonus,
+ * backward, clip_grad_norm_ and torch Adam (bias correction, no weight decay, no amsgrad).  Float32 on the matrix
+ * cores, weights read and written in place in nn.Linear layout.  Handle-free; errors through ch_last_error(NULL).
+ * Supported: 1 or 2 hidden layers per MLP, hidden widths multiples of 16 up to 256, act_dim 1..64, obs_dim >= 1;
+ * anything else is CH_ERR_UNSUPPORTED on entry.  Every sum runs in a fixed order: the same state gives the same
+ * bits.  All pointers are device pointers unless a call says "host only". */
+typedef struct ch_ppo_net {
+    int32_t obs_dim, act_dim;
+    int32_t n_pi, n_vf;        /* hidden layers of the policy / value MLP: 1 or 2 */
+    int32_t pi[2], vf[2];      /* their widths */
+    float* pi_weight[3];       /* mlp_extractor.policy_net's Linear layers, then action_net at [n_pi] */
+    float* pi_bias[3];
+    float* vf_weight[3];       /* mlp_extractor.value_net's Linear layers, then value_net at [n_vf] */
+    float* vf_bias[3];
+    float* log_std;            /* [act_dim] */
+} ch_ppo_net;
+
+typedef struct ch_ppo_hparams {
+    double learning_rate, beta1, beta2, eps;    /* Adam (SB3: 3e-4, 0.9, 0.999, 1e-5) */
+    double clip_range, ent_coef, vf_coef, max_grad_norm;
+    int32_t normalize_advantage;
+    int32_t _pad;
+} ch_ppo_hparams;
+
+/* The flattened rollout buffer (RolloutBuffer.get's arrays): obs [rows][obs_dim], actions [rows][act_dim],
+ * old_log_prob, advantages, returns [rows]. */
+typedef struct ch_ppo_data {
+    const float* obs;
+    const float* actions;
+    const float* old_log_prob;
+    const float* advantages;
+    const float* returns;
+    int64_t rows;
+} ch_ppo_data;
+
+/* Host only.  Replaces: sum(p.numel() for p in policy.parameters()).  The number of parameters, which is the length
+ * of the flat gradient and of Adam's m and v; -1 for an unsupported net.  The flat order is that of
+ * cattleherd.ppo.SB3ActorCritic.parameters(): policy MLP (weight, bias per layer), value MLP, action_net, value_net,
+ * log_std.  The net's pointers are not read. */
+int64_t ch_ppo_param_count(const ch_ppo_net* net);
+
+/* Host only.  No reference counterpart (torch autograd keeps its own buffers): floats of device scratch the calls
+ * below need for minibatches of up to batch_size rows; -1 for an unsupported net or batch_size < 1. */
+int64_t ch_ppo_scratch_size(const ch_ppo_net* net, int64_t batch_size);
+
+/* Replaces: PPO.train's loss.backward() for one minibatch (evaluate_actions, the three loss terms, autograd).
+ * idx: int64 [batch], rows of `data`; PRECONDITION 0 <= idx[i] < data->rows (not checked on the device).
+ * grad_flat [param_count] receives the gradient (unclipped); stats4 = policy loss, value loss (the MSE, without
+ * vf_coef), mean entropy, gradient L2 norm.  Nothing is updated.  scratch: 16-byte aligned. */
+int ch_ppo_grad(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
+                int64_t batch, float* grad_flat, float* stats4, float* scratch, void* stream);
+
+/* Replaces: torch.nn.utils.clip_grad_norm_(policy.parameters(), max_grad_norm) and policy.optimizer.step() (Adam)
+ * from a given flat gradient: coefficient min(1, max_grad_norm / (norm + 1e-6)), then Adam on the net's weights in
+ * place with m, v [param_count] and the step count *step_dev (int64, incremented on the device). */
+int ch_ppo_adam(const ch_ppo_net* net, const ch_ppo_hparams* hp, const float* grad_flat, float* m, float* v,
+                int64_t* step_dev, float* scratch, void* stream);
+
+/* Replaces: one epoch of PPO.train's loop over RolloutBuffer.get(batch_size): ceil(n_idx / batch_size) consecutive
+ * minibatch steps (gradient, clip, Adam) over idx (int64 [n_idx], a permutation drawn by the caller; the same
+ * precondition as ch_ppo_grad), the last one partial if batch_size does not divide n_idx.  Stream-ordered, no host
+ * synchronisation.  stats: NULL or [steps][4] as in ch_ppo_grad. */
+int ch_ppo_train(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
+                 int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
