@@ -475,6 +475,82 @@ int ch_ppo_train(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_d
                  int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
                  void* stream);
 
+/* ---- Native PPO minibatch update for the DTDE (RLlib) driver's shared policy ---------------------------------
+ * Replaces: the minibatch step of RLlib 2.x's new-API-stack PPO learner (PPOTorchLearner.compute_loss_for_module,
+ * the optimizer step) for the DTDE driver's shared policy (DTDECattleHerder.py:62-97), with RLlib's defaults.  The
+ * module: actor encoder (tanh MLP) -> pi, whose 2 * act_dim outputs are the DiagGaussian's mean then raw log_std,
+ * log_std = clamp(raw, -log_std_clip, log_std_clip) with torch.clamp's gradient (k_marl_store applies the same
+ * clamp when sampling); a critic encoder of its own (vf_share_layers False) -> vf.  Loss of a minibatch of B rows:
+ *   mean(-min(A ratio, A clamp(ratio, 1 - clip_param, 1 + clip_param)) + vf_loss_coeff clamp((V - R)^2, 0,
+ *   vf_clip_param) - entropy_coeff H) + kl_coeff mean(KL(sampling policy || current)),
+ * advantages taken as given (the caller standardises them once per training iteration), kl_coeff read from device
+ * memory at each step; then an optional global-norm clip and torch Adam.  The kernels are ch_ppo.hip's, compiled
+ * for this loss and head.  RLlib is not installed here: restated from its source and defaults ("parity unpinned").
+ * Supported: 1 or 2 hidden layers per encoder, widths multiples of 16 up to 256, act_dim 1..32, obs_dim >= 1;
+ * anything else is CH_ERR_UNSUPPORTED on entry.  Handle-free; errors through ch_last_error(NULL).  The same state
+ * gives the same bits.  All pointers are device pointers unless a call says "host only". */
+typedef struct ch_marl_ppo_net {
+    int32_t obs_dim, act_dim;
+    int32_t n_actor, n_critic;     /* hidden layers of the actor / critic encoder: 1 or 2 */
+    int32_t actor[2], critic[2];   /* their widths */
+    float* actor_weight[3];        /* encoder.actor_encoder's Linear layers, then pi [2 * act_dim][.] at [n_actor] */
+    float* actor_bias[3];
+    float* critic_weight[3];       /* encoder.critic_encoder's Linear layers, then vf at [n_critic] */
+    float* critic_bias[3];
+} ch_marl_ppo_net;
+
+typedef struct ch_marl_ppo_hparams {
+    double learning_rate, beta1, beta2, eps;    /* Adam (RLlib: 5e-5, 0.9, 0.999, 1e-8) */
+    double clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff;   /* (RLlib: 0.3, 10, 1, 0) */
+    double log_std_clip;                        /* (RLlib: 20) */
+    double grad_clip;                           /* global-norm clip; <= 0: none (RLlib's default) */
+    const float* kl_coeff_dev;                  /* one float on the device, read by each step (RLlib starts at 0.2) */
+} ch_marl_ppo_hparams;
+
+/* The live agents' rows of a DTDE rollout: obs [rows][obs_dim], actions [rows][act_dim], old_log_prob [rows],
+ * old_dist_inputs [rows][2 * act_dim] (the sampling policy's mean, then its clamped log_std), advantages [rows]
+ * (already standardised), value_targets [rows]. */
+typedef struct ch_marl_ppo_data {
+    const float* obs;
+    const float* actions;
+    const float* old_log_prob;
+    const float* old_dist_inputs;
+    const float* advantages;
+    const float* value_targets;
+    int64_t rows;
+} ch_marl_ppo_data;
+
+/* Host only.  Replaces: sum(p.numel() for p in module.parameters()).  The length of the flat gradient and of
+ * Adam's m and v; -1 for an unsupported net.  The flat order is that of cattleherd.marl_ppo.RLlibActorCritic
+ * .parameters(): actor encoder (weight, bias per layer), critic encoder, pi, vf.  The net's pointers are not read.
+ * With -1 (here and from ch_marl_ppo_scratch_size) the reason is what ch_last_error(NULL) returns next. */
+int64_t ch_marl_ppo_param_count(const ch_marl_ppo_net* net);
+
+/* Host only.  No reference counterpart (torch autograd keeps its own buffers): floats of device scratch the calls
+ * below need for minibatches of up to batch_size rows; -1 for an unsupported net or batch_size < 1. */
+int64_t ch_marl_ppo_scratch_size(const ch_marl_ppo_net* net, int64_t batch_size);
+
+/* Replaces: the learner's compute_losses + backward for one minibatch.  idx: int64 [batch], rows of `data`;
+ * PRECONDITION 0 <= idx[i] < data->rows (not checked on the device).  grad_flat [param_count] receives the gradient
+ * (unclipped); stats5 = policy loss (-mean surrogate), value loss (mean clipped squared error, without
+ * vf_loss_coeff), mean entropy, mean KL, gradient L2 norm.  Nothing is updated.  scratch: 16-byte aligned. */
+int ch_marl_ppo_grad(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
+                     const int64_t* idx, int64_t batch, float* grad_flat, float* stats5, float* scratch, void* stream);
+
+/* Replaces: the learner's gradient clipping (grad_clip_by "global_norm": coefficient min(1, grad_clip / (norm +
+ * 1e-6)); exactly 1 when grad_clip <= 0) and its Adam step from a given flat gradient, on the net's weights in place
+ * with m, v [param_count] and the step count *step_dev (int64, incremented on the device). */
+int ch_marl_ppo_adam(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const float* grad_flat, float* m,
+                     float* v, int64_t* step_dev, float* scratch, void* stream);
+
+/* Replaces: one epoch of the learner's minibatch loop: ceil(n_idx / batch_size) consecutive minibatch steps
+ * (gradient, clip, Adam) over idx (int64 [n_idx], drawn by the caller from the live rows; the same precondition as
+ * ch_marl_ppo_grad), the last one partial if batch_size does not divide n_idx (RLlib's cyclic iterator would wrap
+ * around instead).  Stream-ordered, no host synchronisation.  stats: NULL or [steps][5] as in ch_marl_ppo_grad. */
+int ch_marl_ppo_train(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
+                      const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
+                      float* stats, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,8 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_get_eval", "ch_builtin_spawn_table", "ch_rollout_store", "ch_rollout_post", "ch_rollout_gae", "ch_rollout_collect",
            "ch_spawn_table", "ch_mlp_forward", "ch_mlp_forward_masked", "ch_policy_forward", "ch_mlp_packed_size",
            "ch_mlp_pack", "ch_outputs_to_host", "ch_marl_rollout_collect", "ch_ppo_param_count", "ch_ppo_scratch_size",
-           "ch_ppo_grad", "ch_ppo_adam", "ch_ppo_train")
+           "ch_ppo_grad", "ch_ppo_adam", "ch_ppo_train", "ch_marl_ppo_param_count", "ch_marl_ppo_scratch_size",
+           "ch_marl_ppo_grad", "ch_marl_ppo_adam", "ch_marl_ppo_train")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -116,6 +117,7 @@ def lib():
             getattr(L, name).restype = ctypes.c_int
     L.ch_mlp_packed_size.restype = ctypes.c_int64
     L.ch_ppo_param_count.restype = L.ch_ppo_scratch_size.restype = ctypes.c_int64
+    L.ch_marl_ppo_param_count.restype = L.ch_marl_ppo_scratch_size.restype = ctypes.c_int64
     _lib = L
     return L
 

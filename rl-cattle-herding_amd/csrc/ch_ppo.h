@@ -9,7 +9,7 @@ namespace ch {
 
 constexpr int kPpoTile = 16;        // minibatch rows per workgroup of the forward / backward kernel
 constexpr int kPpoMaxHidden = 256;  // widest hidden layer
-constexpr int kPpoMaxAct = 64;      // widest action
+constexpr int kPpoMaxAct = 64;      // widest policy head (SB3: act_dim; RLlib: 2 * act_dim, the mean then log_std)
 constexpr int kPpoMaxSeg = 13;      // parameter tensors: 2 nets x 3 layers x (weight, bias) + log_std
 
 // one MLP of the actor-critic: n_hidden tanh layers, then the linear head (action_net / value_net)
@@ -22,17 +22,29 @@ struct PpoMlp {
     long long goff_b[3];
 };
 
+// The loss / head flavour the three kernels are compiled for.
+//   kPpoSb3    SB3 PPO.train: the head is the mean, log_std a free parameter; per-minibatch advantage normalisation,
+//              MSE value loss, clip_grad_norm_.
+//   kPpoRllib  RLlib's PPO learner for the shared DTDE policy: the head is [mean, raw log_std] (log_std = the raw
+//              value clamped to +-log_std_clip), no free log_std; the KL penalty with its coefficient read from the
+//              device, the clipped value loss, advantages taken as given, the global-norm clip optional.
+enum PpoFlavour { kPpoSb3 = 0, kPpoRllib = 1 };
+
 struct PpoNet {
-    PpoMlp net[2];       // 0 the policy MLP + action_net, 1 the value MLP + value_net
-    float* log_std;
+    PpoMlp net[2];       // 0 the policy MLP + action_net (RLlib: actor encoder + pi), 1 the value MLP + value_net
+    float* log_std;      // kPpoSb3 only
     long long goff_log_std;
     long long n_params;
     int obs_dim, act_dim;
+    int flavour;
 };
 
 struct PpoHp {
-    double lr, beta1, beta2, eps, clip_range, ent_coef, vf_coef, max_grad_norm;
+    double lr, beta1, beta2, eps, clip_range, ent_coef, vf_coef, max_grad_norm;   // max_grad_norm <= 0 (kPpoRllib): no clip
     int normalize_advantage;
+    // kPpoRllib
+    double vf_clip, log_std_clip;
+    const float* kl_coeff_dev;
 };
 
 struct PpoData {
@@ -42,13 +54,15 @@ struct PpoData {
     const float* advantages;
     const float* returns;
     long long rows;
+    const float* old_dist;   // kPpoRllib: [rows][2 * act_dim], the mean then the clamped log_std of the sampling policy
 };
 
 // Scratch (floats) for minibatches of up to `batch` rows, rows padded to whole tiles (bp):
 //   per net: act[l] [bp][dims[l + 1]] hidden activations (l < n_hidden), dz[l] [bp][dims[l + 1]] (every layer)
 //   tile_stat [tiles][2]   sums of the surrogate minimum and of the squared value error
-//   tile_dls  [tiles][act] log_std gradient partials
-//   misc      [4]          mean entropy
+//             (kPpoRllib: [tiles][4], with the sums of the rows' entropies and KL divergences)
+//   tile_dls  [tiles][act] log_std gradient partials (kPpoSb3)
+//   misc      [4]          mean entropy (kPpoSb3)
 //   partial   [workgroups] sum-of-squares partials of the gradient, one per workgroup that produced a piece of it
 //   grad      [n_params]   the flat gradient (ch_ppo_train)
 struct PpoScratch {
@@ -61,7 +75,8 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s);
 // weight-gradient grid; `bump_step` makes the latter increment *step_dev (the Adam step this gradient is for).
 // ppo_launch_sumsq: the sum-of-squares partials of a given flat gradient (ch_ppo_adam), increments *step_dev.
 // ppo_launch_adam: every workgroup sums the partials in order, forms the clip coefficient and updates its slice;
-// workgroup 0 writes stats4 when it is not NULL.  ppo_launch_stats: stats4 alone (ch_ppo_grad).
+// workgroup 0 writes stats4 when it is not NULL.  ppo_launch_stats: stats4 alone (ch_ppo_grad).  With a kPpoRllib net
+// the statistics are five: policy loss, clipped value loss, mean entropy, mean KL, gradient norm.
 hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
                            float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
                            hipStream_t st);

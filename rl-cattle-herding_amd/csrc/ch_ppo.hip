@@ -15,6 +15,11 @@
 //               torch's Adam on its slice.  The step count was incremented by k_ppo_dw, so the loop over minibatches
 //               is stream-ordered with no host sync.
 //
+// The three kernels take a compile-time flavour (ch_ppo.h).  kPpoRllib is the minibatch step of RLlib's PPO learner for
+// the DTDE driver's shared policy (cattleherd/marl_ppo.py restates it): the head is [mean, raw log_std], the loss adds
+// the KL penalty against the gathered old dist inputs and clips the value error, k_ppo_dw has no log_std workgroup and
+// k_ppo_adam a no-clip mode and five statistics.  kPpoSb3 is the step described above, unchanged.
+//
 // MFMA operand map (16x16x4 f32): lane l gives A[row l & 15][k slot l >> 4] and B[k slot l >> 4][col l & 15]; it
 // holds C/D[row 4 (l >> 4) + r][col l & 15] in register r.  Which k a slot stands for is free as long as A and B
 // agree, so a lane loads four consecutive k as one float4 and feeds element j to the j-th MFMA of the chunk.
@@ -136,8 +141,16 @@ struct FbArgs {
     int normalize;
     int vec_obs;       // obs rows take float4 loads
     int vec_w[2][3];   // so do layer li's weight rows of net ni
+    // kPpoRllib
+    float ent_coef, vf_clip, ls_clip;
+    const float* kl_coeff_dev;
 };
 
+// per-tile loss partials: the surrogate and the squared value error; kPpoRllib adds the entropy and the KL
+template <int F>
+constexpr int kStat = F == kPpoRllib ? 4 : 2;
+
+template <int F>
 __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
     __shared__ __align__(16) float hs[2][kPpoTile * kLdh];   // hidden activations
     __shared__ __align__(16) float dzs[kPpoTile * kLdh];     // dZ of the last hidden layer
@@ -201,57 +214,127 @@ __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
 
     // the loss and its gradient with respect to the head's output, rows past the minibatch 0
     const int NO = net.dims[L];
-    if (ni == 0) {
-        // 16 lanes per row: log-probability of the stored action under N(mean, exp(log_std))
-        const int row = tid >> 4, sub = tid & 15;
-        if (row < kPpoTile) {
-            const bool valid = row0 + row < a.batch;
-            const long long src = a.idx[min(row0 + row, a.batch - 1)];
-            float lp = 0.0f;
-            for (int j = sub; j < NO; j += 16) {
-                const float ls = a.n.log_std[j], dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
-                lp += -(dlt * dlt) / (2.0f * expf(2.0f * ls)) - ls - kHalfLog2Pi;
-            }
+    if constexpr (F == kPpoRllib) {
+        if (ni == 0) {
+            // 16 lanes per row.  The head is [mean (A), raw log_std (A)], log_std = the raw value clamped to +-ls_clip
+            // (torch.clamp: the gradient passes inside the closed range).  Per row: the log-probability of the stored
+            // action, the entropy, and KL(sampling policy || this one) against the gathered old dist inputs.
+            const int row = tid >> 4, sub = tid & 15, A = NO >> 1;
+            if (row < kPpoTile) {
+                const bool valid = row0 + row < a.batch;
+                const long long src = a.idx[min(row0 + row, a.batch - 1)];
+                float lp = 0.0f, ent = 0.0f, kl = 0.0f;
+                for (int j = sub; j < A; j += 16) {
+                    const float mu = os[row * kLdo + j];
+                    const float ls = fminf(fmaxf(os[row * kLdo + A + j], -a.ls_clip), a.ls_clip);
+                    const float mu_p = a.d.old_dist[src * NO + j], ls_p = a.d.old_dist[src * NO + A + j];
+                    const float var = expf(2.0f * ls), dlt = a.d.actions[src * A + j] - mu, dm = mu_p - mu;
+                    lp += -(dlt * dlt) / (2.0f * var) - ls - kHalfLog2Pi;
+                    ent += ls + 0.5f + kHalfLog2Pi;
+                    kl += ls - ls_p + (expf(2.0f * ls_p) + dm * dm) / (2.0f * var) - 0.5f;
+                }
 #pragma unroll
-            for (int o = 8; o > 0; o >>= 1) lp += __shfl_xor(lp, o);
-            float adv = a.d.advantages[src];
-            if (a.normalize && B > 1) adv = (adv - adv_mean) * adv_scale;
-            const float ratio = expf(lp - a.d.old_log_prob[src]);
-            const float s1 = adv * ratio;
-            const float s2 = adv * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
-            // torch.min's gradient goes to the smaller branch (both when they tie: inside the clip range, where the
-            // clamp passes it on); the clamped branch outside the range has none
-            const float dlp = valid && s1 <= s2 ? -inv_b * adv * ratio : 0.0f;
-            if (sub == 0) rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
-            for (int j = sub; j < NO; j += 16) {
-                const float var = expf(2.0f * a.n.log_std[j]);
-                const float dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
-                tmp[row * kLdo + j] = dlp * (dlt * dlt / var - 1.0f);
-                os[row * kLdo + j] = dlp * dlt / var;   // d loss / d mean (each lane its own columns)
+                for (int o = 8; o > 0; o >>= 1) {
+                    lp += __shfl_xor(lp, o);
+                    ent += __shfl_xor(ent, o);
+                    kl += __shfl_xor(kl, o);
+                }
+                const float adv = a.d.advantages[src];   // standardised once per training iteration by the caller
+                const float ratio = expf(lp - a.d.old_log_prob[src]);
+                const float s1 = adv * ratio;
+                const float s2 = adv * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
+                const float dlp = valid && s1 <= s2 ? -inv_b * adv * ratio : 0.0f;   // (torch.min: see kPpoSb3 below)
+                const float klc = valid ? *a.kl_coeff_dev * inv_b : 0.0f, entc = valid ? a.ent_coef * inv_b : 0.0f;
+                if (sub == 0) {
+                    rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
+                    tmp[row] = valid ? ent : 0.0f;
+                    tmp[kPpoTile + row] = valid ? kl : 0.0f;
+                }
+                for (int j = sub; j < A; j += 16) {   // (each lane reads, then overwrites, its own columns)
+                    const float mu = os[row * kLdo + j], raw = os[row * kLdo + A + j];
+                    const float ls = fminf(fmaxf(raw, -a.ls_clip), a.ls_clip);
+                    const float mu_p = a.d.old_dist[src * NO + j], ls_p = a.d.old_dist[src * NO + A + j];
+                    const float var = expf(2.0f * ls), dlt = a.d.actions[src * A + j] - mu, dm = mu_p - mu;
+                    const float dls = dlp * (dlt * dlt / var - 1.0f) - entc + klc * (1.0f - (expf(2.0f * ls_p) + dm * dm) / var);
+                    os[row * kLdo + j] = dlp * dlt / var - klc * dm / var;
+                    os[row * kLdo + A + j] = raw >= -a.ls_clip && raw <= a.ls_clip ? dls : 0.0f;
+                }
+            }
+        } else if (tid < kPpoTile) {
+            // clamp((V - R)^2, 0, vf_clip): the gradient passes where the squared error is inside the closed range
+            const bool valid = row0 + tid < a.batch;
+            const long long src = a.idx[min(row0 + tid, a.batch - 1)];
+            const float err = os[tid * kLdo] - a.d.returns[src], e2 = err * err;
+            rowstat[tid] = valid ? fminf(e2, a.vf_clip) : 0.0f;
+            os[tid * kLdo] = valid && e2 <= a.vf_clip ? a.vf_coef * 2.0f * err * inv_b : 0.0f;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            float s = 0.0f, e = 0.0f, k = 0.0f;
+            for (int r = 0; r < kPpoTile; ++r) s += rowstat[r];
+            a.scratch[a.s.tile_stat + 4 * tile + ni] = s;
+            if (ni == 0) {
+                for (int r = 0; r < kPpoTile; ++r) {
+                    e += tmp[r];
+                    k += tmp[kPpoTile + r];
+                }
+                a.scratch[a.s.tile_stat + 4 * tile + 2] = e;
+                a.scratch[a.s.tile_stat + 4 * tile + 3] = k;
             }
         }
-    } else if (tid < kPpoTile) {
-        const bool valid = row0 + tid < a.batch;
-        const long long src = a.idx[min(row0 + tid, a.batch - 1)];
-        const float err = os[tid * kLdo] - a.d.returns[src];
-        rowstat[tid] = valid ? err * err : 0.0f;
-        os[tid * kLdo] = valid ? a.vf_coef * 2.0f * err * inv_b : 0.0f;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.0f;
-        for (int r = 0; r < kPpoTile; ++r) s += rowstat[r];
-        a.scratch[a.s.tile_stat + 2 * tile + ni] = s;
-        if (ni == 0 && tile == 0) {
-            float e = 0.0f;
-            for (int j = 0; j < NO; ++j) e += 0.5f + kHalfLog2Pi + a.n.log_std[j];
-            a.scratch[a.s.misc] = e;   // the entropy is the same for every row
+    } else {
+        if (ni == 0) {
+            // 16 lanes per row: log-probability of the stored action under N(mean, exp(log_std))
+            const int row = tid >> 4, sub = tid & 15;
+            if (row < kPpoTile) {
+                const bool valid = row0 + row < a.batch;
+                const long long src = a.idx[min(row0 + row, a.batch - 1)];
+                float lp = 0.0f;
+                for (int j = sub; j < NO; j += 16) {
+                    const float ls = a.n.log_std[j], dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
+                    lp += -(dlt * dlt) / (2.0f * expf(2.0f * ls)) - ls - kHalfLog2Pi;
+                }
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) lp += __shfl_xor(lp, o);
+                float adv = a.d.advantages[src];
+                if (a.normalize && B > 1) adv = (adv - adv_mean) * adv_scale;
+                const float ratio = expf(lp - a.d.old_log_prob[src]);
+                const float s1 = adv * ratio;
+                const float s2 = adv * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
+                // torch.min's gradient goes to the smaller branch (both when they tie: inside the clip range, where the
+                // clamp passes it on); the clamped branch outside the range has none
+                const float dlp = valid && s1 <= s2 ? -inv_b * adv * ratio : 0.0f;
+                if (sub == 0) rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
+                for (int j = sub; j < NO; j += 16) {
+                    const float var = expf(2.0f * a.n.log_std[j]);
+                    const float dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
+                    tmp[row * kLdo + j] = dlp * (dlt * dlt / var - 1.0f);
+                    os[row * kLdo + j] = dlp * dlt / var;   // d loss / d mean (each lane its own columns)
+                }
+            }
+        } else if (tid < kPpoTile) {
+            const bool valid = row0 + tid < a.batch;
+            const long long src = a.idx[min(row0 + tid, a.batch - 1)];
+            const float err = os[tid * kLdo] - a.d.returns[src];
+            rowstat[tid] = valid ? err * err : 0.0f;
+            os[tid * kLdo] = valid ? a.vf_coef * 2.0f * err * inv_b : 0.0f;
         }
-    }
-    if (ni == 0 && tid < NO) {
-        float s = 0.0f;
-        for (int r = 0; r < kPpoTile; ++r) s += tmp[r * kLdo + tid];
-        a.scratch[a.s.tile_dls + (long long)tile * NO + tid] = s;
+        __syncthreads();
+        if (tid == 0) {
+            float s = 0.0f;
+            for (int r = 0; r < kPpoTile; ++r) s += rowstat[r];
+            a.scratch[a.s.tile_stat + 2 * tile + ni] = s;
+            if (ni == 0 && tile == 0) {
+                float e = 0.0f;
+                for (int j = 0; j < NO; ++j) e += 0.5f + kHalfLog2Pi + a.n.log_std[j];
+                a.scratch[a.s.misc] = e;   // the entropy is the same for every row
+            }
+        }
+        if (ni == 0 && tid < NO) {
+            float s = 0.0f;
+            for (int r = 0; r < kPpoTile; ++r) s += tmp[r * kLdo + tid];
+            a.scratch[a.s.tile_dls + (long long)tile * NO + tid] = s;
+        }
     }
     for (int i = tid; i < kPpoTile * NO; i += 64 * kFbWaves) {
         const int r = i / NO, j = i - r * NO;
@@ -334,6 +417,7 @@ __device__ __forceinline__ void dw_loop(const DwArgs& a, const DwGemm& G, int n0
     }
 }
 
+template <int F>
 __global__ __launch_bounds__(64 * kDwWaves) void k_ppo_dw(DwArgs a) {
     __shared__ float red[kDwWaves];
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
@@ -341,7 +425,7 @@ __global__ __launch_bounds__(64 * kDwWaves) void k_ppo_dw(DwArgs a) {
     const int wg = blockIdx.x;
     if (wg == 0 && tid == 0 && a.step_dev) *a.step_dev += 1;   // the Adam step this gradient is for
     float ss = 0.0f;
-    if (wg == a.wg_ls) {
+    if (F == kPpoSb3 && wg == a.wg_ls) {   // (kPpoRllib: log_std is a head output, its gradient part of the GEMMs)
         // log_std: the tiles' partials in order, and the entropy bonus (-ent_coef * mean entropy: -ent_coef each)
         if (tid < a.act_dim) {
             float s = 0.0f;
@@ -429,8 +513,9 @@ struct AdamArgs {
     const long long* step_dev;
     const float* partial;
     int n_partials;
-    double lr, beta1, beta2, eps, max_grad_norm;
-    // statistics (stats4 NULL: none): [policy loss, value loss, mean entropy, unclipped gradient norm]
+    double lr, beta1, beta2, eps, max_grad_norm;   // kPpoRllib: max_grad_norm <= 0 is no clip (coefficient exactly 1)
+    // statistics (stats4 NULL: none): [policy loss, value loss, mean entropy, unclipped gradient norm]; kPpoRllib has
+    // five: [policy loss, clipped value loss, mean entropy, mean KL, unclipped gradient norm]
     float* stats4;
     const float* tile_stat;
     const float* misc;
@@ -439,6 +524,7 @@ struct AdamArgs {
     int update;           // 0: statistics only
 };
 
+template <int F>
 __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
     __shared__ float red[4];
     __shared__ float sc[4];
@@ -448,15 +534,25 @@ __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
     const float sumsq = block_sum(s, red, 4);
     const float norm = sqrtf(sumsq);
     if (blockIdx.x == 0 && tid == 0 && a.stats4) {
-        float pl = 0.0f, vl = 0.0f;
+        float pl = 0.0f, vl = 0.0f, en = 0.0f, kl = 0.0f;
         for (int t = 0; t < a.tiles; ++t) {
-            pl += a.tile_stat[2 * t];
-            vl += a.tile_stat[2 * t + 1];
+            pl += a.tile_stat[kStat<F> * t];
+            vl += a.tile_stat[kStat<F> * t + 1];
+            if constexpr (F == kPpoRllib) {
+                en += a.tile_stat[4 * t + 2];
+                kl += a.tile_stat[4 * t + 3];
+            }
         }
         a.stats4[0] = -pl / (float)a.batch;
         a.stats4[1] = vl / (float)a.batch;
-        a.stats4[2] = a.misc[0];
-        a.stats4[3] = norm;
+        if constexpr (F == kPpoRllib) {
+            a.stats4[2] = en / (float)a.batch;
+            a.stats4[3] = kl / (float)a.batch;
+            a.stats4[4] = norm;
+        } else {
+            a.stats4[2] = a.misc[0];
+            a.stats4[3] = norm;
+        }
     }
     if (!a.update) return;
     if (tid == 0) {
@@ -464,6 +560,7 @@ __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
         const double t = (double)*a.step_dev;
         const double bc1 = 1.0 - pow(a.beta1, t), bc2 = 1.0 - pow(a.beta2, t);
         sc[0] = (float)fmin(1.0, a.max_grad_norm / ((double)norm + 1e-6));   // clip_grad_norm_
+        if (F == kPpoRllib && !(a.max_grad_norm > 0.0)) sc[0] = 1.0f;        // grad_clip None
         sc[1] = (float)(a.lr / bc1);
         sc[2] = (float)(1.0 / sqrt(bc2));
     }
@@ -490,7 +587,7 @@ int dw_tiles(int n) { return (n + 15) / 16; }
 int dw_kgroups(int k) { return (k + kDwCols - 1) / kDwCols; }
 
 int dw_workgroups(const PpoNet& n) {
-    int wg = 1;   // log_std
+    int wg = n.flavour == kPpoSb3 ? 1 : 0;   // log_std
     for (int ni = 0; ni < 2; ++ni)
         for (int li = 0; li < n.net[ni].layers; ++li) wg += dw_tiles(n.net[ni].dims[li + 1]) * dw_kgroups(n.net[ni].dims[li]);
     return wg;
@@ -515,8 +612,8 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s) {
             s.dz[ni][li] = take((long long)s.bp * m.dims[li + 1]);
         }
     }
-    s.tile_stat = take(2LL * s.tiles);
-    s.tile_dls = take((long long)s.tiles * n.act_dim);
+    s.tile_stat = take((n.flavour == kPpoRllib ? 4LL : 2LL) * s.tiles);
+    s.tile_dls = take(n.flavour == kPpoSb3 ? (long long)s.tiles * n.act_dim : 0);
     s.misc = take(4);
     s.partial = take(std::max(dw_workgroups(n), kSumsqGrid));
     s.grad = take(n.n_params);
@@ -531,10 +628,13 @@ hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, c
     f.n = n; f.d = d; f.idx = idx; f.batch = batch; f.scratch = scratch; f.s = s;
     f.clip_range = (float)hp.clip_range; f.vf_coef = (float)hp.vf_coef;
     f.normalize = hp.normalize_advantage;
+    f.ent_coef = (float)hp.ent_coef; f.vf_clip = (float)hp.vf_clip; f.ls_clip = (float)hp.log_std_clip;
+    f.kl_coeff_dev = hp.kl_coeff_dev;
     f.vec_obs = n.obs_dim % 4 == 0 && aligned16(d.obs);
     for (int ni = 0; ni < 2; ++ni)
         for (int li = 0; li < n.net[ni].layers; ++li) f.vec_w[ni][li] = n.net[ni].dims[li] % 4 == 0 && aligned16(n.net[ni].w[li]);
-    hipLaunchKernelGGL(k_ppo_fb, dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
+    const bool rllib = n.flavour == kPpoRllib;
+    hipLaunchKernelGGL(rllib ? k_ppo_fb<kPpoRllib> : k_ppo_fb<kPpoSb3>, dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
@@ -556,11 +656,11 @@ hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, c
             wg += dw_tiles(G.N) * G.kgroups;
         }
     }
-    w.wg_ls = wg++;
+    w.wg_ls = rllib ? -1 : wg++;
     w.obs = d.obs; w.idx = idx; w.batch = batch; w.bp = s.bp; w.tiles = s.tiles; w.act_dim = n.act_dim;
     w.tile_dls = scratch + s.tile_dls; w.g_ls = grad + n.goff_log_std; w.ent_coef = (float)hp.ent_coef;
     w.partial = scratch + s.partial; w.step_dev = step_dev;
-    hipLaunchKernelGGL(k_ppo_dw, dim3((unsigned)wg), dim3(64 * kDwWaves), 0, st, w);
+    hipLaunchKernelGGL(rllib ? k_ppo_dw<kPpoRllib> : k_ppo_dw<kPpoSb3>, dim3((unsigned)wg), dim3(64 * kDwWaves), 0, st, w);
     *n_partials = wg;
     return hipGetLastError();
 }
@@ -582,7 +682,7 @@ static void adam_common(AdamArgs& a, const PpoNet& n, float* scratch, const PpoS
             a.seg[a.nseg++] = AdamSeg{m.b[li], m.goff_b[li], (long long)m.dims[li + 1]};
         }
     }
-    a.seg[a.nseg++] = AdamSeg{n.log_std, n.goff_log_std, (long long)n.act_dim};
+    if (n.flavour == kPpoSb3) a.seg[a.nseg++] = AdamSeg{n.log_std, n.goff_log_std, (long long)n.act_dim};
     // by offset, for the kernel's scan (the flat order interleaves the two nets' heads after both MLPs)
     std::sort(a.seg, a.seg + a.nseg, [](const AdamSeg& x, const AdamSeg& y) { return x.off < y.off; });
     a.n_params = n.n_params;
@@ -599,7 +699,7 @@ hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, 
     a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
     a.update = 1;
     const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
-    hipLaunchKernelGGL(k_ppo_adam, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(n.flavour == kPpoRllib ? k_ppo_adam<kPpoRllib> : k_ppo_adam<kPpoSb3>, dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
@@ -607,7 +707,7 @@ hipError_t ppo_launch_stats(const PpoNet& n, float* scratch, const PpoScratch& s
                             float* stats4, hipStream_t st) {
     AdamArgs a;
     adam_common(a, n, scratch, s, n_partials, batch, stats4);
-    hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(n.flavour == kPpoRllib ? k_ppo_adam<kPpoRllib> : k_ppo_adam<kPpoSb3>, dim3(1), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
