@@ -447,11 +447,13 @@ typedef struct ch_ppo_data {
 /* Host only.  Replaces: sum(p.numel() for p in policy.parameters()).  The number of parameters, which is the length
  * of the flat gradient and of Adam's m and v; -1 for an unsupported net.  The flat order is that of
  * cattleherd.ppo.SB3ActorCritic.parameters(): policy MLP (weight, bias per layer), value MLP, action_net, value_net,
- * log_std.  The net's pointers are not read. */
+ * log_std.  The net's pointers are not read.
+ * With -1 (here and from ch_ppo_scratch_size) the reason is what ch_last_error(NULL) returns next. */
 int64_t ch_ppo_param_count(const ch_ppo_net* net);
 
 /* Host only.  No reference counterpart (torch autograd keeps its own buffers): floats of device scratch the calls
- * below need for minibatches of up to batch_size rows; -1 for an unsupported net or batch_size < 1. */
+ * below need for minibatches of up to batch_size rows; -1 for an unsupported net or batch_size < 1, with the reason
+ * as for ch_ppo_param_count. */
 int64_t ch_ppo_scratch_size(const ch_ppo_net* net, int64_t batch_size);
 
 /* Replaces: PPO.train's loss.backward() for one minibatch (evaluate_actions, the three loss terms, autograd).

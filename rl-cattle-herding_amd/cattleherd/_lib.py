@@ -64,6 +64,43 @@ class ChMlp(ctypes.Structure):
                 ("split_out", ctypes.c_int32 * 4), ("split_in", ctypes.c_int32 * 4)]
 
 
+# the native PPO updates' structs (ch_ppo_* for SB3's CTDE policy, ch_marl_ppo_* for RLlib's shared DTDE policy)
+class ChPpoNet(ctypes.Structure):
+    _fields_ = [("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("n_pi", ctypes.c_int32),
+                ("n_vf", ctypes.c_int32), ("pi", ctypes.c_int32 * 2), ("vf", ctypes.c_int32 * 2),
+                ("pi_weight", ctypes.c_void_p * 3), ("pi_bias", ctypes.c_void_p * 3),
+                ("vf_weight", ctypes.c_void_p * 3), ("vf_bias", ctypes.c_void_p * 3), ("log_std", ctypes.c_void_p)]
+
+
+class ChPpoHparams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("learning_rate", "beta1", "beta2", "eps", "clip_range", "ent_coef",
+                                               "vf_coef", "max_grad_norm")] + \
+        [("normalize_advantage", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class ChPpoData(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "actions", "old_log_prob", "advantages", "returns")] + \
+        [("rows", ctypes.c_int64)]
+
+
+class ChMarlPpoNet(ctypes.Structure):
+    _fields_ = [("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("n_actor", ctypes.c_int32),
+                ("n_critic", ctypes.c_int32), ("actor", ctypes.c_int32 * 2), ("critic", ctypes.c_int32 * 2),
+                ("actor_weight", ctypes.c_void_p * 3), ("actor_bias", ctypes.c_void_p * 3),
+                ("critic_weight", ctypes.c_void_p * 3), ("critic_bias", ctypes.c_void_p * 3)]
+
+
+class ChMarlPpoHparams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("learning_rate", "beta1", "beta2", "eps", "clip_param", "vf_clip_param",
+                                               "vf_loss_coeff", "entropy_coeff", "log_std_clip", "grad_clip")] + \
+        [("kl_coeff_dev", ctypes.c_void_p)]
+
+
+class ChMarlPpoData(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "actions", "old_log_prob", "old_dist_inputs", "advantages",
+                                               "value_targets")] + [("rows", ctypes.c_int64)]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -112,6 +149,13 @@ def lib():
     L.ch_mlp_packed_size.argtypes = [P(ChMlp)]
     L.ch_mlp_pack.argtypes = [P(ChMlp), vp, vp]
     L.ch_outputs_to_host.argtypes = [vp, P(ChStepIO), P(ChHostOut), vp]
+    for pre, (N, H, D) in (("ch_ppo_", (P(ChPpoNet), P(ChPpoHparams), P(ChPpoData))),
+                           ("ch_marl_ppo_", (P(ChMarlPpoNet), P(ChMarlPpoHparams), P(ChMarlPpoData)))):
+        getattr(L, pre + "param_count").argtypes = [N]
+        getattr(L, pre + "scratch_size").argtypes = [N, i64]
+        getattr(L, pre + "grad").argtypes = [N, H, D, vp, i64, vp, vp, vp, vp]
+        getattr(L, pre + "adam").argtypes = [N, H, vp, vp, vp, vp, vp, vp]
+        getattr(L, pre + "train").argtypes = [N, H, D, vp, i64, i64, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name != "ch_step_n" or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int

@@ -17,9 +17,11 @@ epoch's last minibatch is partial, where RLlib's cyclic iterator wraps around to
 ``CH_PPO_BACKEND=native``) runs the same minibatch sequence through ``ch_marl_ppo_train`` (csrc/ch_ppo.hip compiled
 for this loss and head): three hand-written launches per step on the parameters' own storage.
 """
-import ctypes
 import math
 import os
+
+from . import _ppo_native
+from ._lib import ChMarlPpoData, ChMarlPpoHparams, ChMarlPpoNet, lib as _bind  # noqa: F401  (their old home)
 
 KEYS = ("encoder.actor_encoder.net.mlp", "encoder.critic_encoder.net.mlp", "pi.net.mlp.0", "vf.net.mlp.0")
 
@@ -120,68 +122,11 @@ class RLlibActorCritic:
         return self.vf(self.critic_encoder(obs)).flatten()
 
 
-class ChMarlPpoNet(ctypes.Structure):
-    _fields_ = [("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("n_actor", ctypes.c_int32),
-                ("n_critic", ctypes.c_int32), ("actor", ctypes.c_int32 * 2), ("critic", ctypes.c_int32 * 2),
-                ("actor_weight", ctypes.c_void_p * 3), ("actor_bias", ctypes.c_void_p * 3),
-                ("critic_weight", ctypes.c_void_p * 3), ("critic_bias", ctypes.c_void_p * 3)]
-
-
-class ChMarlPpoHparams(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_double) for k in ("learning_rate", "beta1", "beta2", "eps", "clip_param", "vf_clip_param",
-                                               "vf_loss_coeff", "entropy_coeff", "log_std_clip", "grad_clip")] + \
-        [("kl_coeff_dev", ctypes.c_void_p)]
-
-
-class ChMarlPpoData(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "actions", "old_log_prob", "old_dist_inputs", "advantages",
-                                               "value_targets")] + [("rows", ctypes.c_int64)]
-
-
-def _bind():
-    from . import _lib
-    lib = _lib.lib()
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    N, H, D = ctypes.POINTER(ChMarlPpoNet), ctypes.POINTER(ChMarlPpoHparams), ctypes.POINTER(ChMarlPpoData)
-    lib.ch_marl_ppo_param_count.argtypes = [N]
-    lib.ch_marl_ppo_scratch_size.argtypes = [N, i64]
-    lib.ch_marl_ppo_grad.argtypes = [N, H, D, vp, i64, vp, vp, vp, vp]
-    lib.ch_marl_ppo_adam.argtypes = [N, H, vp, vp, vp, vp, vp, vp]
-    lib.ch_marl_ppo_train.argtypes = [N, H, D, vp, i64, i64, vp, vp, vp, vp, vp, vp]
-    lib.ch_marl_ppo_param_count.restype = lib.ch_marl_ppo_scratch_size.restype = i64
-    for f in (lib.ch_marl_ppo_grad, lib.ch_marl_ppo_adam, lib.ch_marl_ppo_train):
-        f.restype = ctypes.c_int
-    return lib
-
-
 def marl_ppo_net(model):
     """The ``ch_marl_ppo_net`` over ``model``'s own storage (an ``RLlibActorCritic``), as it is now: it holds raw
     pointers, so build it again after anything that may move a parameter.  Raises ``ValueError`` for an architecture
     the native update does not take, and for parameters that are not contiguous float32 on the model's CUDA device."""
-    def linears(seq):
-        return [m for m in seq if hasattr(m, "weight")]
-    actor, critic = linears(model.actor_encoder), linears(model.critic_encoder)
-    net = ChMarlPpoNet()
-    net.obs_dim, net.act_dim, net.n_actor, net.n_critic = model.obs_dim, model.act_dim, len(actor), len(critic)
-    if not (1 <= len(actor) <= 2 and 1 <= len(critic) <= 2):
-        raise ValueError("native MARL PPO update: each encoder must have 1 or 2 hidden layers")
-    for layers, widths, ws, bs, head in ((actor, net.actor, net.actor_weight, net.actor_bias, model.pi),
-                                         (critic, net.critic, net.critic_weight, net.critic_bias, model.vf)):
-        for i, m in enumerate(layers + [head]):
-            if i < len(layers):
-                widths[i] = m.out_features
-            ws[i], bs[i] = m.weight.data_ptr(), m.bias.data_ptr()
-    lib = _bind()
-    if lib.ch_marl_ppo_param_count(ctypes.byref(net)) < 0:
-        why = (lib.ch_last_error(None) or b"").decode()      # the library's own reason
-        raise ValueError(f"native MARL PPO update: {why} (got obs_dim={model.obs_dim}, act_dim={model.act_dim}, "
-                         f"actor={list(net.actor)[:len(actor)]}, critic={list(net.critic)[:len(critic)]})")
-    for p in model.parameters():
-        if not p.is_cuda or p.device != model.device:
-            raise ValueError("native MARL PPO update: the model must be on a CUDA device (no CPU path exists)")
-        if p.dtype != _torch().float32 or not p.is_contiguous():
-            raise ValueError("native MARL PPO update: parameters must be contiguous float32")
-    return net
+    return _ppo_native.net_struct(_ppo_native.RLLIB, model)
 
 
 STATS = ("policy_loss", "vf_loss", "entropy", "kl", "grad_norm")
@@ -212,12 +157,7 @@ class MarlPPOUpdate:
         if self.minibatch_size < 1 or self.num_epochs < 1:
             raise ValueError("minibatch_size and num_epochs must be >= 1")
         if backend == "native":
-            marl_ppo_net(model)   # raises for an unsupported architecture or a model that is not on the GPU
-            n = sum(p.numel() for p in model.parameters())
-            self.exp_avg = torch.zeros(n, dtype=torch.float32, device=model.device)
-            self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=model.device)
-            self.step_count = torch.zeros(1, dtype=torch.int64, device=model.device)
-            self._scratch = None
+            self._native = _ppo_native.NativeState(_ppo_native.RLLIB, model)   # raises for a model it cannot take
         else:
             self.opt = torch.optim.Adam(model.parameters(), lr=self.lr, betas=self.betas, eps=self.eps)
         self.kl_coeff = torch.full((1,), float(kl_coeff), dtype=torch.float32, device=model.device)
@@ -314,28 +254,19 @@ class MarlPPOUpdate:
     def _train_native(self, data, live, n):
         """The same permutations as the torch path, one ch_marl_ppo_train call per epoch on the current stream."""
         torch = _torch()
-        from ._lib import check
-        lib = _bind()
-        net = marl_ppo_net(self.model)   # the parameters' storage as it is now (a .to() or .data = ... moves it)
+        dev = self.model.device
         data = tuple(t.contiguous() for t in data)
         for t in data:
-            if t.dtype != torch.float32 or t.device != self.model.device:
+            if t.dtype != torch.float32 or t.device != dev:
                 raise ValueError("native MARL PPO update: the rollout buffer must be float32 on the model's device")
-        d = ChMarlPpoData(*(t.data_ptr() for t in data), data[0].shape[0])
         hp = ChMarlPpoHparams(self.lr, self.betas[0], self.betas[1], self.eps, self.clip_param, self.vf_clip_param,
                               self.vf_loss_coeff, self.entropy_coeff, self.log_std_clip,
                               self.grad_clip if self.grad_clip is not None else 0.0, self.kl_coeff.data_ptr())
-        bs = self.minibatch_size
-        nb = (n + bs - 1) // bs
-        want = lib.ch_marl_ppo_scratch_size(ctypes.byref(net), min(bs, n))
-        if self._scratch is None or self._scratch.numel() < want:
-            self._scratch = torch.empty(want, dtype=torch.float32, device=self.model.device)
-        with torch.cuda.device(self.model.device):
-            stream = torch.cuda.current_stream(self.model.device).cuda_stream
-            for e in range(self.num_epochs):
-                perm = live[torch.randperm(n, device=self.model.device, generator=self.gen)]
-                check(lib.ch_marl_ppo_train(ctypes.byref(net), ctypes.byref(hp), ctypes.byref(d), perm.data_ptr(), n,
-                                            bs, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                            self.step_count.data_ptr(), self.stats[e * nb].data_ptr(),
-                                            self._scratch.data_ptr(), stream))
-                # (perm is freed to torch's caching allocator, which is stream-ordered: the launches read it first)
+        self._native.train(hp, ChMarlPpoData(*(t.data_ptr() for t in data), data[0].shape[0]), self.num_epochs, n,
+                           self.minibatch_size, lambda: live[torch.randperm(n, device=dev, generator=self.gen)],
+                           self.stats)
+
+    # Adam's moments over the flat parameters and its step count (native backend)
+    exp_avg = property(lambda self: self._native.exp_avg)
+    exp_avg_sq = property(lambda self: self._native.exp_avg_sq)
+    step_count = property(lambda self: self._native.step_count)

@@ -20,9 +20,11 @@ what an eager loop would measure.
 (csrc/ch_ppo.hip): forward, loss, backward, ``clip_grad_norm_`` and Adam as three hand-written launches per step, on
 the parameters' own storage.  The default stays ``"torch"``.
 """
-import ctypes
 import math
 import os
+
+from . import _ppo_native
+from ._lib import ChPpoData, ChPpoHparams, ChPpoNet, lib as _bind  # noqa: F401  (the structs' and the binding's old home)
 
 
 def _torch():
@@ -93,67 +95,11 @@ class SB3ActorCritic:
         return values.flatten(), log_prob, entropy
 
 
-class ChPpoNet(ctypes.Structure):
-    _fields_ = [("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("n_pi", ctypes.c_int32),
-                ("n_vf", ctypes.c_int32), ("pi", ctypes.c_int32 * 2), ("vf", ctypes.c_int32 * 2),
-                ("pi_weight", ctypes.c_void_p * 3), ("pi_bias", ctypes.c_void_p * 3),
-                ("vf_weight", ctypes.c_void_p * 3), ("vf_bias", ctypes.c_void_p * 3), ("log_std", ctypes.c_void_p)]
-
-
-class ChPpoHparams(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_double) for k in ("learning_rate", "beta1", "beta2", "eps", "clip_range", "ent_coef",
-                                               "vf_coef", "max_grad_norm")] + \
-        [("normalize_advantage", ctypes.c_int32), ("_pad", ctypes.c_int32)]
-
-
-class ChPpoData(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "actions", "old_log_prob", "advantages", "returns")] + \
-        [("rows", ctypes.c_int64)]
-
-
-def _bind():
-    from . import _lib
-    lib = _lib.lib()
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    N, H, D = ctypes.POINTER(ChPpoNet), ctypes.POINTER(ChPpoHparams), ctypes.POINTER(ChPpoData)
-    lib.ch_ppo_param_count.argtypes = [N]
-    lib.ch_ppo_scratch_size.argtypes = [N, i64]
-    lib.ch_ppo_grad.argtypes = [N, H, D, vp, i64, vp, vp, vp, vp]
-    lib.ch_ppo_adam.argtypes = [N, H, vp, vp, vp, vp, vp, vp]
-    lib.ch_ppo_train.argtypes = [N, H, D, vp, i64, i64, vp, vp, vp, vp, vp, vp]
-    lib.ch_ppo_param_count.restype = lib.ch_ppo_scratch_size.restype = i64
-    for f in (lib.ch_ppo_grad, lib.ch_ppo_adam, lib.ch_ppo_train):
-        f.restype = ctypes.c_int
-    return lib
-
-
 def ppo_net(model):
     """The ``ch_ppo_net`` over ``model``'s own storage (an ``SB3ActorCritic``), as it is now: it holds raw pointers, so
     build it again after anything that may move a parameter.  Raises ``ValueError`` for an architecture the native
     update does not take, and for parameters that are not contiguous float32 on the model's CUDA device."""
-    def linears(seq):
-        return [m for m in seq if hasattr(m, "weight")]
-    pi, vf = linears(model.policy_net), linears(model.value_net_mlp)
-    net = ChPpoNet()
-    net.obs_dim, net.act_dim, net.n_pi, net.n_vf = model.obs_dim, model.act_dim, len(pi), len(vf)
-    if not (1 <= len(pi) <= 2 and 1 <= len(vf) <= 2):
-        raise ValueError("native PPO update: each MLP must have 1 or 2 hidden layers")
-    for name, layers, widths, ws, bs, head in (("pi", pi, net.pi, net.pi_weight, net.pi_bias, model.action_net),
-                                               ("vf", vf, net.vf, net.vf_weight, net.vf_bias, model.value_net)):
-        for i, m in enumerate(layers + [head]):
-            if i < len(layers):
-                widths[i] = m.out_features
-            ws[i], bs[i] = m.weight.data_ptr(), m.bias.data_ptr()
-    net.log_std = model.log_std.data_ptr()
-    if _bind().ch_ppo_param_count(ctypes.byref(net)) < 0:
-        raise ValueError("native PPO update: hidden widths must be multiples of 16 and at most 256, act_dim at most 64 "
-                         f"(got pi={list(net.pi)[:len(pi)]}, vf={list(net.vf)[:len(vf)]}, act_dim={model.act_dim})")
-    for p in model.parameters():
-        if not p.is_cuda or p.device != model.device:
-            raise ValueError("native PPO update: the model must be on a CUDA device (no CPU path exists)")
-        if p.dtype != _torch().float32 or not p.is_contiguous():
-            raise ValueError("native PPO update: parameters must be contiguous float32")
-    return net
+    return _ppo_native.net_struct(_ppo_native.SB3, model)
 
 
 class PPOUpdate:
@@ -172,14 +118,9 @@ class PPOUpdate:
         self.backend = backend
         if backend == "native":
             graph = False
-            ppo_net(model)   # raises for an unsupported architecture or a model that is not on the GPU
+            self._native = _ppo_native.NativeState(_ppo_native.SB3, model)   # raises for a model it cannot take
             self._hp = ChPpoHparams(learning_rate, 0.9, 0.999, 1e-5, clip_range, ent_coef, vf_coef, max_grad_norm,
                                     int(bool(normalize_advantage)), 0)
-            n = sum(p.numel() for p in model.parameters())
-            self.exp_avg = torch.zeros(n, dtype=torch.float32, device=model.device)
-            self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=model.device)
-            self.step_count = torch.zeros(1, dtype=torch.int64, device=model.device)
-            self._scratch = None
         self.model = model
         self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
         self.clip_range, self.ent_coef, self.vf_coef = float(clip_range), float(ent_coef), float(vf_coef)
@@ -292,26 +233,16 @@ class PPOUpdate:
     def _train_native(self, data, n, nb):
         """The same permutations as the torch path, one ch_ppo_train call per epoch on the current stream."""
         torch = _torch()
-        from ._lib import check
-        lib = _bind()
-        net = ppo_net(self.model)   # the parameters' storage as it is now (a .to() or .data = ... moves it)
+        dev = self.model.device
         for t in data:
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.model.device:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                 raise ValueError("native PPO update: the rollout buffer must be contiguous float32 on the model's device")
-        d = ChPpoData(*(t.data_ptr() for t in data), n)
-        bs = min(self.batch_size, n)
-        want = lib.ch_ppo_scratch_size(ctypes.byref(net), bs)
-        if self._scratch is None or self._scratch.numel() < want:
-            self._scratch = torch.empty(want, dtype=torch.float32, device=self.model.device)
-        with torch.cuda.device(self.model.device):
-            stream = torch.cuda.current_stream(self.model.device).cuda_stream
-            for _ in range(self.n_epochs):
-                perm = torch.randperm(n, device=self.model.device, generator=self.gen)
-                check(lib.ch_ppo_train(ctypes.byref(net), ctypes.byref(self._hp), ctypes.byref(d),
-                                       perm.data_ptr(), n, self.batch_size, self.exp_avg.data_ptr(),
-                                       self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), None,
-                                       self._scratch.data_ptr(), stream))
-                # (perm is freed to torch's caching allocator, which is stream-ordered: the launches read it first)
-        steps = self.n_epochs * nb
+        steps = self._native.train(self._hp, ChPpoData(*(t.data_ptr() for t in data), n), self.n_epochs, n,
+                                   self.batch_size, lambda: torch.randperm(n, device=dev, generator=self.gen))
         self.sgd_steps += steps
         return steps
+
+    # Adam's moments over the flat parameters and its step count (native backend)
+    exp_avg = property(lambda self: self._native.exp_avg)
+    exp_avg_sq = property(lambda self: self._native.exp_avg_sq)
+    step_count = property(lambda self: self._native.step_count)

@@ -30,6 +30,10 @@ struct PpoMlp {
 //              device, the clipped value loss, advantages taken as given, the global-norm clip optional.
 enum PpoFlavour { kPpoSb3 = 0, kPpoRllib = 1 };
 
+// statistics per minibatch step.  kPpoSb3: policy loss, value loss, mean entropy, gradient norm; kPpoRllib: policy
+// loss, clipped value loss, mean entropy, mean KL, gradient norm.
+constexpr int ppo_n_stats(PpoFlavour f) { return f == kPpoRllib ? 5 : 4; }
+
 struct PpoNet {
     PpoMlp net[2];       // 0 the policy MLP + action_net (RLlib: actor encoder + pi), 1 the value MLP + value_net
     float* log_std;      // kPpoSb3 only
@@ -75,8 +79,8 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s);
 // weight-gradient grid; `bump_step` makes the latter increment *step_dev (the Adam step this gradient is for).
 // ppo_launch_sumsq: the sum-of-squares partials of a given flat gradient (ch_ppo_adam), increments *step_dev.
 // ppo_launch_adam: every workgroup sums the partials in order, forms the clip coefficient and updates its slice;
-// workgroup 0 writes stats4 when it is not NULL.  ppo_launch_stats: stats4 alone (ch_ppo_grad).  With a kPpoRllib net
-// the statistics are five: policy loss, clipped value loss, mean entropy, mean KL, gradient norm.
+// workgroup 0 writes the step's statistics (ppo_n_stats of them) to `stats` when it is not NULL.  ppo_launch_stats: the
+// statistics alone (ch_ppo_grad, ch_marl_ppo_grad).
 hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
                            float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
                            hipStream_t st);
@@ -84,8 +88,8 @@ hipError_t ppo_launch_sumsq(const PpoNet& n, const float* grad, float* scratch, 
                             int* n_partials, hipStream_t st);
 hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, float* m, float* v,
                            const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                           float* stats4, hipStream_t st);
+                           float* stats, hipStream_t st);
 hipError_t ppo_launch_stats(const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                            float* stats4, hipStream_t st);
+                            float* stats, hipStream_t st);
 
 }  // namespace ch

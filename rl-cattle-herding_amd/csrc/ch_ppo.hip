@@ -673,7 +673,7 @@ hipError_t ppo_launch_sumsq(const PpoNet& n, const float* grad, float* scratch, 
 }
 
 static void adam_common(AdamArgs& a, const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                        float* stats4) {
+                        float* stats) {
     std::memset(&a, 0, sizeof(a));
     for (int ni = 0; ni < 2; ++ni) {
         const PpoMlp& m = n.net[ni];
@@ -687,14 +687,14 @@ static void adam_common(AdamArgs& a, const PpoNet& n, float* scratch, const PpoS
     std::sort(a.seg, a.seg + a.nseg, [](const AdamSeg& x, const AdamSeg& y) { return x.off < y.off; });
     a.n_params = n.n_params;
     a.partial = scratch + s.partial; a.n_partials = n_partials;
-    a.stats4 = stats4; a.tile_stat = scratch + s.tile_stat; a.misc = scratch + s.misc; a.tiles = s.tiles; a.batch = batch;
+    a.stats4 = stats; a.tile_stat = scratch + s.tile_stat; a.misc = scratch + s.misc; a.tiles = s.tiles; a.batch = batch;
 }
 
 hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, float* m, float* v,
                            const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                           float* stats4, hipStream_t st) {
+                           float* stats, hipStream_t st) {
     AdamArgs a;
-    adam_common(a, n, scratch, s, n_partials, batch, stats4);
+    adam_common(a, n, scratch, s, n_partials, batch, stats);
     a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
     a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
     a.update = 1;
@@ -704,9 +704,9 @@ hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, 
 }
 
 hipError_t ppo_launch_stats(const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                            float* stats4, hipStream_t st) {
+                            float* stats, hipStream_t st) {
     AdamArgs a;
-    adam_common(a, n, scratch, s, n_partials, batch, stats4);
+    adam_common(a, n, scratch, s, n_partials, batch, stats);
     hipLaunchKernelGGL(n.flavour == kPpoRllib ? k_ppo_adam<kPpoRllib> : k_ppo_adam<kPpoSb3>, dim3(1), dim3(256), 0, st, a);
     return hipGetLastError();
 }

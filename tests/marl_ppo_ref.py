@@ -9,7 +9,7 @@ import types
 import numpy as np
 import torch
 
-from ppo_native_ref import FACTOR, FLOOR, err  # noqa: F401
+from ppo_native_ref import FACTOR, FLOOR, accept, err, split_flat  # noqa: F401
 
 # RLlib's defaults, with a learning rate at which a few steps move the parameters well above float32 roundoff
 HP = dict(lr=3e-4, eps=1e-8, clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2,
@@ -232,33 +232,12 @@ def check_conditions(aux, hp, clamp=False, stats=None):
         assert (raw > c).any() and (raw < -c).any() and (np.abs(raw) < c).any()
 
 
-def accept(name, native, t32, ref):
-    """Print the two errors, then hold the native one to the rule.  A tensor that is exactly zero in the reference
-    (the gradient of a branch whose loss terms are switched off) has no scale: the native one must be zero too."""
-    if float(ref.abs().max()) == 0.0:
-        print(f"{name}: reference is exactly 0, native max {float(native.abs().max()):.3e}")
-        return float(native.abs().max()) == 0.0
-    en, et = err(native, ref), err(t32, ref)
-    bound = FACTOR * max(et, FLOOR)
-    print(f"{name}: err(native) {en:.3e}  err(torch32) {et:.3e}  bound {bound:.3e}")
-    return en <= bound
-
-
 def param_names(model):
     names = []
     for k, seq in (("actor", model.actor_encoder), ("critic", model.critic_encoder)):
         for i, m in enumerate(x for x in seq if hasattr(x, "weight")):
             names += [f"{k}{i}.weight", f"{k}{i}.bias"]
     return names + ["pi.weight", "pi.bias", "vf.weight", "vf.bias"]
-
-
-def split_flat(flat, model):
-    out, o = [], 0
-    for p in model.parameters():
-        out.append(flat[o:o + p.numel()].view_as(p))
-        o += p.numel()
-    assert o == flat.numel()
-    return out
 
 
 def fake_buffer(rb, dtype):

@@ -85,6 +85,19 @@ def test_backend_switch(monkeypatch):
                       backend="native")
 
 
+def test_host_only_calls_leave_their_reason():
+    from cattleherd import ppo
+    lib = ppo._bind()
+    assert lib.ch_ppo_param_count(ctypes.byref(_net(obs_dim=0))) == -1
+    assert lib.ch_last_error(None) == b"ch_ppo_param_count: obs_dim must be >= 1"
+    assert lib.ch_ppo_scratch_size(ctypes.byref(_net(pi=(24, 128))), 64) == -1
+    assert lib.ch_last_error(None).startswith(b"ch_ppo_scratch_size: ")
+    # the message is the library's own reason, not one text for every rejection
+    with pytest.raises(ValueError, match=r"act_dim must be 1\.\.64"):
+        ppo.PPOUpdate(ppo.SB3ActorCritic(obs_dim=172, act_dim=65, pi=(32,), vf=(32,), device="cpu"), graph=False,
+                      backend="native")
+
+
 @pytest.mark.parametrize("which,batch", [("DRIVER", 64), ("DRIVER", 40), ("DRIVER", 8), ("DRIVER", 1), ("SMALL", 24),
                                          ("DENSE", 24), ("DRIVER_DENSE", 40)])
 def test_synthetic_minibatches_meet_the_clip_conditions(which, batch):
