@@ -149,6 +149,10 @@ def lib():
     L.ch_mlp_packed_size.argtypes = [P(ChMlp)]
     L.ch_mlp_pack.argtypes = [P(ChMlp), vp, vp]
     L.ch_outputs_to_host.argtypes = [vp, P(ChStepIO), P(ChHostOut), vp]
+    if hasattr(L, "ch__mlp_last_launch"):   # internal (tests / diagnostics): see mlp_last_launch below
+        L.ch__mlp_last_launch.argtypes = [P(i32 * 4)]
+        L.ch__mlp_launch_counts.argtypes = [P(i64 * len(MLP_KERNELS))]
+        L.ch__mlp_last_launch.restype = L.ch__mlp_launch_counts.restype = ctypes.c_int
     for pre, (N, H, D) in (("ch_ppo_", (P(ChPpoNet), P(ChPpoHparams), P(ChPpoData))),
                            ("ch_marl_ppo_", (P(ChMarlPpoNet), P(ChMarlPpoHparams), P(ChMarlPpoData)))):
         getattr(L, pre + "param_count").argtypes = [N]
@@ -171,6 +175,26 @@ def check(rc, handle=None):
         msg = lib().ch_last_error(handle)
         raise ChError(rc, msg.decode() if msg else "")
     return rc
+
+
+# Internal (tests / diagnostics): ch__mlp_last_launch's kernel numbers, as k_mlp2<NW, TW, SHARE, RT> / k_mlp<NW, TWMAX, DEPTH>
+MLP_KERNELS = ("none", "k_mlp2<8,1>", "k_mlp2<8,2>", "k_mlp2<4,2>", "k_mlp2<8,1,true>", "k_mlp2<8,1,false,2>",
+               "k_mlp2<4,4,false,2>", "k_mlp2<4,4,false,4>", "k_mlp<8,1,2>", "k_mlp<8,2,2>", "k_mlp<4,4,1>")
+
+
+def mlp_last_launch():
+    """Internal (tests / diagnostics): (kernel name, row tiles per workgroup, grid, dynamic LDS bytes) of the policy
+    forward launched last in this process (ch__mlp_last_launch; kept on the host, no device work)."""
+    out = (ctypes.c_int32 * 4)()
+    check(lib().ch__mlp_last_launch(ctypes.byref(out)))
+    return MLP_KERNELS[out[0]], int(out[1]), int(out[2]), int(out[3])
+
+
+def mlp_launch_counts():
+    """Internal (tests / diagnostics): {kernel name: launches since the library was loaded} (ch__mlp_launch_counts)."""
+    out = (ctypes.c_int64 * len(MLP_KERNELS))()
+    check(lib().ch__mlp_launch_counts(ctypes.byref(out)))
+    return {k: int(v) for k, v in zip(MLP_KERNELS, out)}
 
 
 def default_config(mode, num_drones, num_cattle):

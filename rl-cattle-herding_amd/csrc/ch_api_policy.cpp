@@ -120,6 +120,25 @@ int ch__set_mlp_tstamp(long long* dev) {
     return CH_OK;
 }
 
+/* Internal (tests / diagnostics): the forward kernel the last ch_mlp_forward / ch_policy_forward / collection launch
+ * ran (launch_mlp_multi's record; host side): out = {kernel, row tiles per workgroup, grid, dynamic LDS bytes}.
+ * kernel: 0 nothing launched (no rows); k_mlp2<NW, TW, SHARE, RT> 1 <8,1>, 2 <8,2>, 3 <4,2>, 4 <8,1,true>,
+ * 5 <8,1,false,2>, 6 <4,4,false,2>, 7 <4,4,false,4>; k_mlp<NW, TWMAX, DEPTH> 8 <8,1,2>, 9 <8,2,2>, 10 <4,4,1>. */
+int ch__mlp_last_launch(int32_t out[4]) {
+    if (!out) return CH_ERR_INVALID;
+    out[0] = g_mlp_last_launch.kernel; out[1] = g_mlp_last_launch.rt;
+    out[2] = g_mlp_last_launch.grid; out[3] = g_mlp_last_launch.lds;
+    return CH_OK;
+}
+
+/* Internal (tests / diagnostics): launches of each forward kernel since the library was loaded, indexed by
+ * ch__mlp_last_launch's kernel number (11 counters) -- a collection launches several; a test takes the difference. */
+int ch__mlp_launch_counts(int64_t out[11]) {
+    if (!out) return CH_ERR_INVALID;
+    for (int i = 0; i < kMlpKernels; ++i) out[i] = g_mlp_launches[i];
+    return CH_OK;
+}
+
 /* Internal (tests / diagnostics): ch_rollout_collect's path, bit 0 copy each step's observation into the buffer
  * (CH_ROLLOUT_COPY=1), bit 1 the stand-alone store kernel instead of the forward epilogues (CH_ROLLOUT_STORE_KERNEL=1),
  * bit 2 the actor forward fused into the step (CH_FUSED_ACTOR=1), bit 3 never fused. */

@@ -249,6 +249,20 @@ struct MlpMulti {
 hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const int* roles = nullptr,
                             const RolloutArgs* ro = nullptr);
 bool mlp_multi_fits(const MlpArgs* segs, int nseg);   // k_mlp2 takes these nets (the rollout epilogues need it)
+// diagnostics (ch__mlp_last_launch): which forward kernel launch_mlp_multi launched last -- host side only.
+// kMlp2_<NW>_<TW>[s][_r<RT>] = k_mlp2<NW, TW, SHARE, RT>; kMlp1_<NW>_<TWMAX>_<DEPTH> = k_mlp<NW, TWMAX, DEPTH>
+enum MlpKernel {
+    kMlpNone = 0, kMlp2_8_1 = 1, kMlp2_8_2 = 2, kMlp2_4_2 = 3, kMlp2_8_1s = 4, kMlp2_8_1_r2 = 5, kMlp2_4_4_r2 = 6,
+    kMlp2_4_4_r4 = 7, kMlp1_8_1_2 = 8, kMlp1_8_2_2 = 9, kMlp1_4_4_1 = 10, kMlpKernels = 11
+};
+struct MlpLaunch {
+    int kernel;   // MlpKernel (kMlpNone: no row to compute, nothing launched)
+    int rt;       // row tiles of 16 per workgroup it ended with
+    int grid;     // workgroups
+    int lds;      // dynamic LDS bytes
+};
+extern MlpLaunch g_mlp_last_launch;
+extern long long g_mlp_launches[kMlpKernels];   // launches of each kernel since the library was loaded
 
 template <class R> hipError_t launch_step(const StepParams<R>& p, int team, hipStream_t st);
 template <class R> hipError_t launch_reset(const StepParams<R>& p, int team, hipStream_t st);

@@ -17,7 +17,8 @@ constexpr int kWMax = 256;         // widest layer
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-// tanh(v) = 1 - 2 / (exp(2v) + 1) on the hardware exp2 and reciprocal: an absolute error of a few 1e-8 (the relative
+// tanh(v) = 1 - 2 / (exp(2v) + 1) on the hardware exp2 and reciprocal: an absolute error of at most 7.4 x 2^-24 = 4.4e-7
+// (derived in tests/mlp_ref.py; 2e-7 measured over tests/test_gpu_mlp_variants.py's sweep) (the relative
 // error of a small |v| is larger -- the tests hold the forward's outputs, i.e. absolute errors of the hidden units
 // summed through the next layer, to 1e-5 and 2e-5), about 8 instructions instead of ocml's tanhf.  A 64-row tile
 // applies it to 64 values per lane and layer, which made the epilogues as long as the matrix loops.
@@ -71,6 +72,16 @@ struct Ring2 {
 template <int TW, int RT> constexpr int ring_depth() { return TW * RT >= 8 ? 2 : kD2; }
 
 __device__ __host__ __forceinline__ int pad_pairs(int k) { return ((k + 31) / 32 + kD2 - 1) / kD2 * kD2; }
+
+// mlp2_body's staging ring: 4 NW threads share an input row, each holding kQ float4 registers per pass.  A pass must
+// cover a whole row tile's padded width 32 np0 (the store loop walks the ring once per pass), so a kernel takes only
+// first layers with ceil(8 np0 / (4 NW)) <= kQ.  <8, *, *> rings hold kMaxPair0 pairs; the <4, 4, *, RT > 1> ones
+// (8 registers, to stay inside their register budget) hold 16 pairs = 512 columns: launch_mlp_multi gives wider
+// first layers one row tile per workgroup.
+template <int NW, int RT> constexpr int mlp2_stage_regs() { return RT > 1 && NW < 8 ? 8 : 8 * kMaxPair0 / (4 * NW); }
+template <int NW, int RT> __host__ __device__ constexpr bool mlp2_stage_fits(int np0) {
+    return (8 * np0 + 4 * NW - 1) / (4 * NW) <= mlp2_stage_regs<NW, RT>();
+}
 
 // the wave's weight source for one layer: per tile, the packed tile's lane base, or the raw row
 template <int TW>
@@ -394,8 +405,11 @@ __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int l
     mlp2_prologue_s<NW, TW, ring_depth<TW, RT>(), PKO>(d1, d0, pkp0, vw, pk, w0, pko0, 0, pl, ring, ws, wave, lane);
     if (ts) ts[1] = clock64();
     const int np0 = min(pad_pairs(max(kcap, 1)), kMaxPair0);
-    // rows srow + 16 rt; as many row tiles per pass as the kQ registers hold (RT nld <= kQ for the reference's nets)
-    constexpr int kTPR = 4 * NW, kQ = RT > 1 && NW < 8 ? 8 : 8 * kMaxPair0 / kTPR;   // (RT > 1: more passes, fewer registers)
+    // rows srow + 16 rt; as many row tiles per pass as the kQ registers hold (RT nld <= kQ for the reference's nets;
+    // nld <= kQ always: mlp2_stage_fits, which the host checks for the 8-register rings)
+    constexpr int kTPR = 4 * NW, kQ = mlp2_stage_regs<NW, RT>();   // (RT > 1: more passes, fewer registers)
+    static_assert(mlp2_stage_fits<NW, RT>(kMaxPair0) || (NW == 4 && RT > 1 && mlp2_stage_fits<NW, RT>(16)),
+                  "a staging pass covers the widest first layer the host sends this kernel");
     const int K0 = d0, srow = tid / kTPR, sc = 4 * (tid % kTPR), nld = (8 * np0 + kTPR - 1) / kTPR;
     const int rper = max(1, min(RT, kQ / nld));
     const bool vec_x = (vw >> 7) & 1, vec2_x = !vec_x && (K0 & 1) == 0 && K0 >= 2 && (reinterpret_cast<uintptr_t>(x) & 7) == 0;

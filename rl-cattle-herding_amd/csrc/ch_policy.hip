@@ -28,6 +28,8 @@
 namespace ch {
 
 long long* g_mlp_tstamp = nullptr;
+MlpLaunch g_mlp_last_launch = {kMlpNone, 0, 0, 0};
+long long g_mlp_launches[kMlpKernels] = {};
 
 namespace {
 
@@ -338,6 +340,13 @@ static bool mlp2_shape(const MlpArgs& a, int& maxw, int& lda, int& ldh) {
     const int np0 = pad_pairs(std::max(a.kcap, 1));
     lda = (32 * np0 + 63) / 64 * 64 + 4;
     ldh = (std::max(maxhid, 32 * kD2) + 32 * kD2 - 1) / (32 * kD2) * (32 * kD2) + 4;
+    // Raw weights and a hidden width that is no multiple of 16: the layer's last tile clamps its rows past the width
+    // to the last weight row (packed weights hold zero rows there), so its epilogue writes non-zero activations into
+    // the columns [N, 16 nt) that other waves zero for the next layer, with no barrier between the two.  Those nets
+    // go to k_mlp, which masks the columns in its epilogue.
+    bool ragged = false;
+    for (int i = 1; i < a.layers; ++i) ragged |= a.dims[i] % 16 != 0;
+    if (!a.packed && ragged) return false;
     return np0 <= kMaxPair0 && sizeof(float) * mlp2_lds_floats(1, lda, ldh) <= (size_t)kLdsMax2;
 }
 
@@ -386,8 +395,12 @@ hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const
         for (int r : {4, 2})
             if (rows_all >= (long long)kTM * r * cus) { rt = r; break; }
     rt = std::min(rt, maxw0 > 128 ? 4 : (nw4 ? 1 : 2));   // the instantiations below
-    for (int s = 0; s < nseg; ++s)
+    for (int s = 0; s < nseg; ++s) {
         if (maxw0 > 128 && !segs[s].packed) rt = 1;          // the wide row-tiled kernels read packed weights only
+        // ... and stage a row tile's input in one pass of their 8-register ring: a wider live first layer (kcap > 512)
+        // runs one row tile per workgroup (<8, 2>), whose ring holds any width k_mlp2 takes
+        if (maxw0 > 128 && rt > 1 && !mlp2_stage_fits<4, 2>(pad_pairs(std::max(segs[s].kcap, 1)))) rt = 1;
+    }
     MlpMulti m;
     int maxw = 0, fits = 0, grid = 0, n = 0;
     for (;;) {   // the largest rt <= the chosen one whose tile fits the LDS
@@ -409,28 +422,40 @@ hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const
         if (rt == 1 || sizeof(float) * mlp2_lds_floats(rt, m.lda, m.ldh) <= (size_t)kLdsMax2) break;
         rt >>= 1;
     }
-    if (n == 0) return hipSuccess;
+    const auto record = [&](int kernel, int g, size_t lds) {
+        g_mlp_last_launch = MlpLaunch{kernel, rt, g, (int)lds};
+        ++g_mlp_launches[kernel];
+    };
+    if (n == 0) { record(kMlpNone, 0, 0); return hipSuccess; }
     if (ro) m.ro = *ro;
     m.nseg = n;
     m.start[n] = grid;
     const size_t lds2 = sizeof(float) * mlp2_lds_floats(rt, m.lda, m.ldh);
     if (fits && lds2 <= (size_t)kLdsMax2) {
+        int kernel;
         if (maxw > 128) {
             // RT > 1: four waves of 64 columns each, one per SIMD (the 512-register budget of a lone wave holds the
             // 4 x 4 accumulators and the 4 x 4 weight ring)
+            kernel = rt == 4 ? kMlp2_4_4_r4 : (rt == 2 ? kMlp2_4_4_r2 : kMlp2_8_2);
             if (rt == 4) hipLaunchKernelGGL((k_mlp2<4, 4, false, 4>), dim3((unsigned)grid), dim3(256), lds2, st, m);
             else if (rt == 2) hipLaunchKernelGGL((k_mlp2<4, 4, false, 2>), dim3((unsigned)grid), dim3(256), lds2, st, m);
             else hipLaunchKernelGGL((k_mlp2<8, 2>), dim3((unsigned)grid), dim3(512), lds2, st, m);
-        } else if (nw4) hipLaunchKernelGGL((k_mlp2<4, 2>), dim3((unsigned)grid), dim3(256), lds2, st, m);
-        else if (n > 1 && rt == 1) {   // two workgroups per CU (128 registers)
+        } else if (nw4) {
+            kernel = kMlp2_4_2;
+            hipLaunchKernelGGL((k_mlp2<4, 2>), dim3((unsigned)grid), dim3(256), lds2, st, m);
+        } else if (n > 1 && rt == 1) {   // two workgroups per CU (128 registers)
+            kernel = kMlp2_8_1s;
             hipLaunchKernelGGL((k_mlp2<8, 1, true>), dim3((unsigned)grid), dim3(512), lds2, st, m);
         } else {
+            kernel = rt >= 2 ? kMlp2_8_1_r2 : kMlp2_8_1;
             if (rt >= 2) hipLaunchKernelGGL((k_mlp2<8, 1, false, 2>), dim3((unsigned)grid), dim3(512), lds2, st, m);
             else hipLaunchKernelGGL((k_mlp2<8, 1>), dim3((unsigned)grid), dim3(512), lds2, st, m);
         }
+        record(kernel, grid, lds2);
         return hipGetLastError();
     }
     // the round-2 kernel, one launch per net (no rollout epilogues: callers check mlp_multi_fits first)
+    rt = 1;
     for (int s = 0; s < n; ++s) {
         if (m.role[s] != kRoleNone) return hipErrorInvalidValue;
         const MlpArgs& a = m.seg[s];
@@ -440,6 +465,7 @@ hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const
         if (w <= 128) hipLaunchKernelGGL((k_mlp<8, 1, 2>), dim3(g), dim3(512), mlp_lds_bytes(), st, a);
         else if (wide4) hipLaunchKernelGGL((k_mlp<4, 4, 1>), dim3(g), dim3(256), mlp_lds_bytes(), st, a);
         else hipLaunchKernelGGL((k_mlp<8, 2, 2>), dim3(g), dim3(512), mlp_lds_bytes(), st, a);
+        record(w <= 128 ? kMlp1_8_1_2 : (wide4 ? kMlp1_4_4_1 : kMlp1_8_2_2), (int)g, mlp_lds_bytes());
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
