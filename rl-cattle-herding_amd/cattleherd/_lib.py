@@ -153,6 +153,11 @@ def lib():
         L.ch__mlp_last_launch.argtypes = [P(i32 * 4)]
         L.ch__mlp_launch_counts.argtypes = [P(i64 * len(MLP_KERNELS))]
         L.ch__mlp_last_launch.restype = L.ch__mlp_launch_counts.restype = ctypes.c_int
+    if hasattr(L, "ch__mlp_plan"):   # internal: the host-only planner and its kernel table, see mlp_plan below
+        L.ch__mlp_kernel.argtypes = [i32, P(i32 * 8)]
+        L.ch__mlp_kernel.restype = ctypes.c_char_p
+        L.ch__mlp_plan.argtypes = [P(P(ChMlp)), P(i64), P(i32), i32, i32, i32, i32, i32, i32, P(i32 * 12)]
+        L.ch__mlp_plan.restype = ctypes.c_int
     for pre, (N, H, D) in (("ch_ppo_", (P(ChPpoNet), P(ChPpoHparams), P(ChPpoData))),
                            ("ch_marl_ppo_", (P(ChMarlPpoNet), P(ChMarlPpoHparams), P(ChMarlPpoData)))):
         getattr(L, pre + "param_count").argtypes = [N]
@@ -195,6 +200,37 @@ def mlp_launch_counts():
     out = (ctypes.c_int64 * len(MLP_KERNELS))()
     check(lib().ch__mlp_launch_counts(ctypes.byref(out)))
     return {k: int(v) for k, v in zip(MLP_KERNELS, out)}
+
+
+MLP_KERNEL_COLUMNS = ("family", "nw", "tw", "share", "rt", "packed_only", "max_pair0", "raw_ragged")
+
+
+def mlp_kernel_table():
+    """Internal (tests / diagnostics): the library's forward-kernel table (csrc/ch_mlp_plan.h kMlpTable), one dict per
+    row in ch__mlp_last_launch's numbering: its name and MLP_KERNEL_COLUMNS (family: 2 k_mlp2, 1 k_mlp, 0 none)."""
+    rows = []
+    while True:
+        out = (ctypes.c_int32 * 8)()
+        name = lib().ch__mlp_kernel(len(rows), ctypes.byref(out))
+        if name is None:
+            return rows
+        rows.append(dict(zip(MLP_KERNEL_COLUMNS, (int(v) for v in out)), name=name.decode()))
+
+
+def mlp_plan(nets, rows, cus, kcap=None, v1=False, nw4=False, wide4=False, rt=0):
+    """Internal (tests / diagnostics): what a forward of up to three ``nets`` (ChMlp; only dims, n_layers, packed and
+    non-NULL weights matter) over ``rows`` rows each would launch on a device of ``cus`` compute units under the given
+    switches (CH_MLP_V1, CH_MLP2_NW4, CH_MLP_WIDE4, CH_MLP_RT) -- planned on the host, no device needed.  ``kcap``:
+    live input widths (0: dims[0]).  Returns a dict: v2, rt, lda, ldh, lds, and kernel names and grids per live segment."""
+    n = len(nets)
+    ptrs = (ctypes.POINTER(ChMlp) * n)(*[ctypes.pointer(m) for m in nets])
+    out = (ctypes.c_int32 * 12)()
+    check(lib().ch__mlp_plan(ptrs, (ctypes.c_int64 * n)(*rows), (ctypes.c_int32 * n)(*(kcap or [0] * n)), n, cus,
+                             int(v1), int(nw4), int(wide4), rt, ctypes.byref(out)))
+    v = [int(x) for x in out]
+    live = v[5]
+    return {"v2": bool(v[0]), "rt": v[1], "lda": v[2], "ldh": v[3], "lds": v[4],
+            "kernel": [MLP_KERNELS[k] for k in v[6:6 + live]], "grid": v[9:9 + live]}
 
 
 def default_config(mode, num_drones, num_cattle):

@@ -122,8 +122,8 @@ int ch__set_mlp_tstamp(long long* dev) {
 
 /* Internal (tests / diagnostics): the forward kernel the last ch_mlp_forward / ch_policy_forward / collection launch
  * ran (launch_mlp_multi's record; host side): out = {kernel, row tiles per workgroup, grid, dynamic LDS bytes}.
- * kernel: 0 nothing launched (no rows); k_mlp2<NW, TW, SHARE, RT> 1 <8,1>, 2 <8,2>, 3 <4,2>, 4 <8,1,true>,
- * 5 <8,1,false,2>, 6 <4,4,false,2>, 7 <4,4,false,4>; k_mlp<NW, TWMAX, DEPTH> 8 <8,1,2>, 9 <8,2,2>, 10 <4,4,1>. */
+ * kernel: the row of the kernel table (ch_mlp_plan.h kMlpTable, MlpKernel; ch__mlp_kernel gives a row's name and
+ * columns), 0 = nothing launched (no rows). */
 int ch__mlp_last_launch(int32_t out[4]) {
     if (!out) return CH_ERR_INVALID;
     out[0] = g_mlp_last_launch.kernel; out[1] = g_mlp_last_launch.rt;
@@ -136,6 +136,40 @@ int ch__mlp_last_launch(int32_t out[4]) {
 int ch__mlp_launch_counts(int64_t out[11]) {
     if (!out) return CH_ERR_INVALID;
     for (int i = 0; i < kMlpKernels; ++i) out[i] = g_mlp_launches[i];
+    return CH_OK;
+}
+
+/* Internal (tests / diagnostics): row `kernel` of the kernel table: its name (NULL past the table) and, if `out` is
+ * given, {family (2 k_mlp2, 1 k_mlp, 0 none), NW, TW, SHARE, RT, packed weights only, the most first-layer K pairs it
+ * stages, takes raw weights with ragged hidden widths}. */
+const char* ch__mlp_kernel(int32_t kernel, int32_t out[8]) {
+    if (kernel < 0 || kernel >= kMlpKernels) return nullptr;
+    const MlpKernelInfo& k = kMlpTable[kernel];
+    const int32_t v[8] = {k.family, k.nw, k.tw, k.share, k.rt, k.packed_only, k.max_pair0, k.raw_ragged};
+    if (out) std::copy(v, v + 8, out);
+    return k.name;
+}
+
+/* Internal (tests / diagnostics): what launch_mlp_multi would launch for up to three nets -- mlp_plan on the host, no
+ * device touched.  rows[s]: segment s's row count; kcap (optional) its live input width, 0 = dims[0]; cus: the CU
+ * count to plan for; then the four switches the library otherwise reads from the environment (CH_MLP_V1,
+ * CH_MLP2_NW4, CH_MLP_WIDE4, CH_MLP_RT).  out = {v2, rt, lda, ldh, lds bytes, live segments n, kernel[3], grid[3]}
+ * (kernel and grid per live segment; v2: one launch of kernel[0] over the summed grid). */
+int ch__mlp_plan(const ch_mlp* const* nets, const int64_t* rows, const int32_t* kcap, int32_t nseg, int32_t cus,
+                 int32_t v1, int32_t nw4, int32_t wide4, int32_t rt, int32_t out[12]) {
+    if (!nets || !rows || !out || nseg < 1 || nseg > 3 || cus < 1) return fail(nullptr, CH_ERR_INVALID, "ch__mlp_plan: bad argument");
+    MlpArgs segs[3];
+    float one = 0.0f;
+    for (int s = 0; s < nseg; ++s) {
+        std::string err;
+        const int rc = mlp_args(nets[s], &one, rows[s], &one, segs[s], err);
+        if (rc) return fail(nullptr, rc, "ch__mlp_plan: " + err);
+        if (kcap && kcap[s] > 0) segs[s].kcap = std::min(kcap[s], segs[s].dims[0]);
+    }
+    const MlpPlan p = mlp_plan(segs, nseg, cus, MlpSwitches{v1 != 0, nw4 != 0, wide4 != 0, rt});
+    const int32_t v[12] = {p.v2, p.rt, p.lda, p.ldh, p.lds, p.n, p.kernel[0], p.kernel[1], p.kernel[2],
+                           p.grid[0], p.grid[1], p.grid[2]};
+    std::copy(v, v + 12, out);
     return CH_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/cattleherd.h"
+#include "ch_mlp_plan.h"   // the policy forward's constants, kernel table (MlpKernel, MlpLaunch) and planner
 
 namespace ch {
 
@@ -171,7 +172,6 @@ extern long long* g_mlp_tstamp;
 // floats of the packed layout of an MLP (per-layer offsets / pair counts out, optional)
 long long mlp_packed_floats(int layers, const int* dims, long long* off, int* pairs);
 hipError_t launch_mlp_pack(const MlpArgs& a, float* dst, hipStream_t st);
-size_t mlp_lds_bytes();
 hipError_t launch_mlp(const MlpArgs& a, hipStream_t st);
 
 // ch_aux.hip: metric rows [kMetricRows][E] -> out[CH_METRIC_COUNT] (sums over envs, fixed order);
@@ -248,19 +248,9 @@ struct MlpMulti {
 };
 hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const int* roles = nullptr,
                             const RolloutArgs* ro = nullptr);
-bool mlp_multi_fits(const MlpArgs* segs, int nseg);   // k_mlp2 takes these nets (the rollout epilogues need it)
-// diagnostics (ch__mlp_last_launch): which forward kernel launch_mlp_multi launched last -- host side only.
-// kMlp2_<NW>_<TW>[s][_r<RT>] = k_mlp2<NW, TW, SHARE, RT>; kMlp1_<NW>_<TWMAX>_<DEPTH> = k_mlp<NW, TWMAX, DEPTH>
-enum MlpKernel {
-    kMlpNone = 0, kMlp2_8_1 = 1, kMlp2_8_2 = 2, kMlp2_4_2 = 3, kMlp2_8_1s = 4, kMlp2_8_1_r2 = 5, kMlp2_4_4_r2 = 6,
-    kMlp2_4_4_r4 = 7, kMlp1_8_1_2 = 8, kMlp1_8_2_2 = 9, kMlp1_4_4_1 = 10, kMlpKernels = 11
-};
-struct MlpLaunch {
-    int kernel;   // MlpKernel (kMlpNone: no row to compute, nothing launched)
-    int rt;       // row tiles of 16 per workgroup it ended with
-    int grid;     // workgroups
-    int lds;      // dynamic LDS bytes
-};
+// launch_mlp_multi's plan for these segments is one k_mlp2 launch (mlp_plan(...).v2: the rollout epilogues need it)
+bool mlp_multi_fits(const MlpArgs* segs, int nseg);
+// diagnostics (ch__mlp_last_launch): which forward kernel (ch_mlp_plan.h MlpKernel) launch_mlp_multi launched last
 extern MlpLaunch g_mlp_last_launch;
 extern long long g_mlp_launches[kMlpKernels];   // launches of each kernel since the library was loaded
 
@@ -282,7 +272,7 @@ template <class R> hipError_t launch_step_v2_multi(const StepParams<R>& p, const
 // fit it; launch = false checks only.
 template <class R> hipError_t launch_step_v2_actor(const StepParams<R>& p, int block, size_t lds, hipStream_t st,
                                                    const MlpArgs& a, const RolloutArgs& ro, bool launch = true);
-// k_mlp2's one-tile shape for a fused forward (ch_policy.hip): LDS strides and dynamic bytes; false when the net does
+// k_mlp2's one-tile shape for a fused forward (ch_mlp_plan.cpp): LDS strides and dynamic bytes; false when the net does
 // not fit a 12-wave, one-column-tile-per-wave tile (layers <= 192 wide, first-layer live width <= 1152)
 bool mlp2_fused_tile(const MlpArgs& a, int& lda, int& ldh, size_t& bytes);
 // the v2 kernel runs with per-wave env tables (V2Layout W > 0) for herds above this size

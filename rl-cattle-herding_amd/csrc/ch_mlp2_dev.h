@@ -5,15 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include "ch_internal.h"
+#include "ch_mlp_plan.h"   // kTM, kKC, kKS, kWMax, kD2, kMaxPair0, kLdsMax2, pad_pairs, mlp2_stage_regs / _fits, mlp2_pko
 #include "ch_rollout_dev.h"
 
 namespace ch {
 namespace {
-
-constexpr int kTM = 16;            // rows per workgroup
-constexpr int kKC = 64;            // K chunk
-constexpr int kKS = kKC + 4;       // LDS row stride of a chunk (conflict-free operand reads)
-constexpr int kWMax = 256;         // widest layer
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -60,28 +56,12 @@ __device__ __forceinline__ float act_fn(float v, int act) {
 // meets a zero), and the pair count is padded to a multiple of D: no load is conditional, so the compiler's vmcnt
 // waits count exactly the D - 1 younger pairs instead of draining every load in flight.
 
-constexpr int kD2 = 4;         // K pairs in flight per wave
-constexpr int kMaxPair0 = 36;  // first-layer live width <= 1152 (else k_mlp)
-constexpr int kLdsMax2 = 160 * 1024 - 1024;   // k_mlp2 dynamic LDS cap (the static kmax word included)
-
 // D pairs in flight (kD2; 2 when a pair's MFMAs already take ~1 k cycles: TW x RT >= 8 tiles per wave)
 template <int TW, int D = kD2>
 struct Ring2 {
     float4 v[D][TW][2];
 };
 template <int TW, int RT> constexpr int ring_depth() { return TW * RT >= 8 ? 2 : kD2; }
-
-__device__ __host__ __forceinline__ int pad_pairs(int k) { return ((k + 31) / 32 + kD2 - 1) / kD2 * kD2; }
-
-// mlp2_body's staging ring: 4 NW threads share an input row, each holding kQ float4 registers per pass.  A pass must
-// cover a whole row tile's padded width 32 np0 (the store loop walks the ring once per pass), so a kernel takes only
-// first layers with ceil(8 np0 / (4 NW)) <= kQ.  <8, *, *> rings hold kMaxPair0 pairs; the <4, 4, *, RT > 1> ones
-// (8 registers, to stay inside their register budget) hold 16 pairs = 512 columns: launch_mlp_multi gives wider
-// first layers one row tile per workgroup.
-template <int NW, int RT> constexpr int mlp2_stage_regs() { return RT > 1 && NW < 8 ? 8 : 8 * kMaxPair0 / (4 * NW); }
-template <int NW, int RT> __host__ __device__ constexpr bool mlp2_stage_fits(int np0) {
-    return (8 * np0 + 4 * NW - 1) / (4 * NW) <= mlp2_stage_regs<NW, RT>();
-}
 
 // the wave's weight source for one layer: per tile, the packed tile's lane base, or the raw row
 template <int TW>
@@ -352,7 +332,7 @@ __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int l
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long long row0 = blk * TMR;
-    constexpr bool PKO = NW == 4 && RT > 1;   // packed weights only (launch_mlp_multi)
+    constexpr bool PKO = mlp2_pko(NW, RT);   // packed weights only (the kernel table's packed_only)
     // the arguments the tile's start needs -- the live-width scan's and the first layer's (plan, weight fetch, input
     // rows) -- read together and pinned (see mlp2_prologue): one scalar round trip before the first loads (read where
     // each is used, the start of a tile was ~5 k cycles of dependent scalar reads, tools/mlp_marl_probe.py --ctde)
@@ -408,8 +388,8 @@ __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int l
     // rows srow + 16 rt; as many row tiles per pass as the kQ registers hold (RT nld <= kQ for the reference's nets;
     // nld <= kQ always: mlp2_stage_fits, which the host checks for the 8-register rings)
     constexpr int kTPR = 4 * NW, kQ = mlp2_stage_regs<NW, RT>();   // (RT > 1: more passes, fewer registers)
-    static_assert(mlp2_stage_fits<NW, RT>(kMaxPair0) || (NW == 4 && RT > 1 && mlp2_stage_fits<NW, RT>(16)),
-                  "a staging pass covers the widest first layer the host sends this kernel");
+    static_assert(mlp2_stage_pairs<NW, RT>() > 0 && mlp2_stage_fits<NW, RT>(mlp2_stage_pairs<NW, RT>()),
+                  "a staging pass covers the widest first layer the kernel table (max_pair0) sends this kernel");
     const int K0 = d0, srow = tid / kTPR, sc = 4 * (tid % kTPR), nld = (8 * np0 + kTPR - 1) / kTPR;
     const int rper = max(1, min(RT, kQ / nld));
     const bool vec_x = (vw >> 7) & 1, vec2_x = !vec_x && (K0 & 1) == 0 && K0 >= 2 && (reinterpret_cast<uintptr_t>(x) & 7) == 0;

@@ -11,6 +11,14 @@
 // straight into registers; k_mlp (the round-2 kernel, kept for first-layer widths past 1152 and for A/B with
 // CH_MLP_V1=1) streams K chunks of 64 of inputs and weights through LDS.
 //
+// Dispatch.  ch_mlp_plan.h holds one table row per instantiation below (name, NW, TW, SHARE, RT, and what the kernel
+// tolerates: packed weights only, the first-layer K pairs its staging ring holds, ragged raw hidden widths) and
+// ch_mlp_plan.cpp the planner, a pure function of (nets, row counts, CU count, switches): 1. the row tiles asked for,
+// from the launch's rows and the CU count (or CH_MLP_RT); 2. the table rows of the nets' width class that tolerate
+// them; 3. among those the most row tiles whose tile fits the LDS; 4. the SHARE variant for a multi-segment launch at
+// one row tile; 5. k_mlp, one launch per net, when no k_mlp2 row is left or CH_MLP_V1 is set.  launch_mlp_multi (at
+// the end of this file) reads the switches, asks for the plan and launches the row's kernel.
+//
 // Zero input columns.  An observation row has NUM_DRONES live rows of 86 features and zeros after
 // them (BaseRLAviary.py:272-342).  With per-row live widths the tile multiplies only the chunks below
 // its widest live row: the skipped products are 0 * w, which add +-0 to the sums.
@@ -246,7 +254,7 @@ __global__ __launch_bounds__(64 * NW) void k_mlp(MlpArgs a) {
 // other's matrix work -- the rollout's actor, critic and terminal-value critic in one launch.
 // SHARE: registers capped at 128 per lane (4 waves per SIMD) so that two 8-wave workgroups fit a CU -- the
 // multi-segment launches; a single forward runs without the cap (fewer, faster waves: 17-18 vs 19.7 us alone)
-// RT: row tiles of 16 per workgroup (launch_mlp_multi picks 2 or 4 for row counts that fill the chip anyway: each
+// RT: row tiles of 16 per workgroup (mlp_plan picks 2 or 4 for row counts that fill the chip anyway: each
 // weight pair then feeds RT x more MFMAs, the 256-wide RLlib nets' forward is otherwise bound by the weight stream).
 // <4, 4, *, 2> is held to 256 registers so that two workgroups share a CU (one's epilogue beside the other's MFMAs)
 template <int NW, int TW, bool SHARE = false, int RT = 1>
@@ -269,8 +277,6 @@ __global__ void k_mlp_pack(const float* __restrict__ W, int N, int K, int P, flo
 }
 
 }  // namespace
-
-size_t mlp_lds_bytes() { return sizeof(float) * (kTM * kKS + kWMax * kKS + 2 * kTM * (kWMax + 4)); }
 
 long long mlp_packed_floats(int layers, const int* dims, long long* off, int* pairs) {
     long long total = 0;
@@ -296,176 +302,83 @@ hipError_t launch_mlp_pack(const MlpArgs& a, float* dst, hipStream_t st) {
     return hipGetLastError();
 }
 
-static hipError_t mlp_attrs() {
-    // the dynamic-LDS opt-in, once per device (the attribute is per device context)
-    static std::atomic<unsigned long long> attr_set{0};
+// The kernels of ch_mlp_plan.h's table, by MlpKernel (k_mlp2 takes an MlpMulti, k_mlp an MlpArgs).  Each entry names
+// its row; they stand in the order the code object has always held the kernels (it follows their first use here).
+static const void* mlp_fn(int kernel) {
+#define CH_FN(K, ...) case K: return reinterpret_cast<const void*>(&__VA_ARGS__)
+    switch (kernel) {
+        CH_FN(kMlp1_8_1_2, k_mlp<8, 1, 2>); CH_FN(kMlp1_8_2_2, k_mlp<8, 2, 2>); CH_FN(kMlp1_4_4_1, k_mlp<4, 4, 1>);
+        CH_FN(kMlp2_4_2, k_mlp2<4, 2>); CH_FN(kMlp2_8_2, k_mlp2<8, 2>); CH_FN(kMlp2_8_1, k_mlp2<8, 1>);
+        CH_FN(kMlp2_8_1s, k_mlp2<8, 1, true>); CH_FN(kMlp2_4_4_r2, k_mlp2<4, 4, false, 2>);
+        CH_FN(kMlp2_4_4_r4, k_mlp2<4, 4, false, 4>); CH_FN(kMlp2_8_1_r2, k_mlp2<8, 1, false, 2>);
+        default: return nullptr;
+    }
+#undef CH_FN
+}
+
+// once per device (the attribute is per device context): every kernel's dynamic-LDS opt-in and the CU count
+static hipError_t mlp_device(int& cus) {
+    static std::atomic<int> cus_of[64];   // 0: not set up yet
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-        for (const void* f : {reinterpret_cast<const void*>(&k_mlp<8, 1, 2>), reinterpret_cast<const void*>(&k_mlp<8, 2, 2>),
-                              reinterpret_cast<const void*>(&k_mlp<4, 4, 1>)}) {
-            e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_lds_bytes());
-            if (e != hipSuccess) return e;
-        }
-        for (const void* f : {reinterpret_cast<const void*>(&k_mlp2<4, 2>), reinterpret_cast<const void*>(&k_mlp2<8, 2>),
-                              reinterpret_cast<const void*>(&k_mlp2<8, 1>), reinterpret_cast<const void*>(&k_mlp2<8, 1, true>),
-                              reinterpret_cast<const void*>(&k_mlp2<4, 4, false, 2>),
-                              reinterpret_cast<const void*>(&k_mlp2<4, 4, false, 4>),
-                              reinterpret_cast<const void*>(&k_mlp2<8, 1, false, 2>)}) {
-            e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax2);
-            if (e != hipSuccess) return e;
-        }
-        attr_set.fetch_or(bit, std::memory_order_relaxed);
+    std::atomic<int>& slot = cus_of[dev & 63];
+    if ((cus = slot.load(std::memory_order_relaxed)) > 0) return hipSuccess;
+    for (int k = 1; k < kMlpKernels; ++k) {
+        e = hipFuncSetAttribute(mlp_fn(k), hipFuncAttributeMaxDynamicSharedMemorySize, kMlpTable[k].lds_attr());
+        if (e != hipSuccess) return e;
     }
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    slot.store(cus, std::memory_order_relaxed);
     return hipSuccess;
 }
 
-// k_mlp2's shape for one net: widest layer, LDS strides (the live input width rounded to whole K pairs, rows
-// padded to 4 mod 64 floats); false when the net does not fit it (then k_mlp)
-// LDS floats of k_mlp2's tile: RT == 1 input rows and two hidden buffers; RT > 1 the odd layers' hidden buffer in the
-// input rows' region (dead after layer 0)
-static size_t mlp2_lds_floats(int rt, int lda, int ldh) {
-    return rt == 1 ? (size_t)kTM * (lda + 2 * ldh) : (size_t)kTM * rt * ((lda > ldh ? lda : ldh) + ldh);
-}
-
-static bool mlp2_shape(const MlpArgs& a, int& maxw, int& lda, int& ldh) {
-    int maxhid = 32;
-    maxw = 0;
-    for (int i = 1; i <= a.layers; ++i) {
-        maxw = a.dims[i] > maxw ? a.dims[i] : maxw;
-        maxhid = a.dims[i] > maxhid ? a.dims[i] : maxhid;   // (the output too: the sampling epilogue stages there)
-    }
-    const int np0 = pad_pairs(std::max(a.kcap, 1));
-    lda = (32 * np0 + 63) / 64 * 64 + 4;
-    ldh = (std::max(maxhid, 32 * kD2) + 32 * kD2 - 1) / (32 * kD2) * (32 * kD2) + 4;
-    // Raw weights and a hidden width that is no multiple of 16: the layer's last tile clamps its rows past the width
-    // to the last weight row (packed weights hold zero rows there), so its epilogue writes non-zero activations into
-    // the columns [N, 16 nt) that other waves zero for the next layer, with no barrier between the two.  Those nets
-    // go to k_mlp, which masks the columns in its epilogue.
-    bool ragged = false;
-    for (int i = 1; i < a.layers; ++i) ragged |= a.dims[i] % 16 != 0;
-    if (!a.packed && ragged) return false;
-    return np0 <= kMaxPair0 && sizeof(float) * mlp2_lds_floats(1, lda, ldh) <= (size_t)kLdsMax2;
-}
-
-bool mlp2_fused_tile(const MlpArgs& a, int& lda, int& ldh, size_t& bytes) {
-    int maxw = 0;
-    if (!mlp2_shape(a, maxw, lda, ldh) || maxw > 16 * (CH_V2_MAX_BLOCK / 64)) return false;
-    if (a.rows_dev || a.row_mask || a.rows_per_env != 1) return false;
-    bytes = sizeof(float) * mlp2_lds_floats(1, lda, ldh);
-    return true;
+// the A/B switches, read once per process
+static const MlpSwitches& mlp_switches() {
+    static const MlpSwitches sw = [] {
+        const auto on = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
+        const char* rt = getenv("CH_MLP_RT");
+        return MlpSwitches{on("CH_MLP_V1"), on("CH_MLP2_NW4"), on("CH_MLP_WIDE4"), rt ? atoi(rt) : 0};
+    }();
+    return sw;
 }
 
 bool mlp_multi_fits(const MlpArgs* segs, int nseg) {
-    static const bool v1 = [] { const char* v = getenv("CH_MLP_V1"); return v && v[0] == '1'; }();
-    if (v1) return false;
-    for (int s = 0; s < nseg; ++s) {
-        int w, la, lh;
-        if (!mlp2_shape(segs[s], w, la, lh)) return false;
-    }
-    return true;
+    int cus = 0;
+    return nseg >= 1 && nseg <= 3 && mlp_device(cus) == hipSuccess && mlp_plan(segs, nseg, cus, mlp_switches()).v2;
 }
 
 hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const int* roles, const RolloutArgs* ro) {
-    static const bool v1 = [] { const char* v = getenv("CH_MLP_V1"); return v && v[0] == '1'; }();
-    static const bool nw4 = [] { const char* v = getenv("CH_MLP2_NW4"); return v && v[0] == '1'; }();   // A/B
-    static const bool wide4 = [] { const char* v = getenv("CH_MLP_WIDE4"); return v && v[0] == '1'; }();
     if (nseg < 1 || nseg > 3) return hipErrorInvalidValue;
-    hipError_t e = mlp_attrs();
+    int cus = 0;
+    hipError_t e = mlp_device(cus);
     if (e != hipSuccess) return e;
-    // row tiles per workgroup: the most (1, 2 or 4 tiles of 16 rows) that still leave a workgroup for every CU across
-    // the launch's segments -- each weight pair a workgroup streams then feeds RT times the MFMAs, and the forward of
-    // a chip-filling batch waits on that stream, not on the matrix cores; CH_MLP_RT overrides
-    static const int rt_env = [] { const char* v = getenv("CH_MLP_RT"); return v ? atoi(v) : 0; }();
-    int maxw0 = 0, cus = 256;
-    long long rows_all = 0;
-    for (int s = 0; s < nseg; ++s) {
-        for (int i = 1; i <= segs[s].layers; ++i) maxw0 = std::max(maxw0, segs[s].dims[i]);
-        rows_all += segs[s].rows;
-    }
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    }
-    int rt = 1;
-    if (rt_env == 1 || rt_env == 2 || rt_env == 4) rt = rt_env;
-    else
-        for (int r : {4, 2})
-            if (rows_all >= (long long)kTM * r * cus) { rt = r; break; }
-    rt = std::min(rt, maxw0 > 128 ? 4 : (nw4 ? 1 : 2));   // the instantiations below
-    for (int s = 0; s < nseg; ++s) {
-        if (maxw0 > 128 && !segs[s].packed) rt = 1;          // the wide row-tiled kernels read packed weights only
-        // ... and stage a row tile's input in one pass of their 8-register ring: a wider live first layer (kcap > 512)
-        // runs one row tile per workgroup (<8, 2>), whose ring holds any width k_mlp2 takes
-        if (maxw0 > 128 && rt > 1 && !mlp2_stage_fits<4, 2>(pad_pairs(std::max(segs[s].kcap, 1)))) rt = 1;
-    }
-    MlpMulti m;
-    int maxw = 0, fits = 0, grid = 0, n = 0;
-    for (;;) {   // the largest rt <= the chosen one whose tile fits the LDS
-        std::memset(&m, 0, sizeof(m));
-        maxw = 0; fits = !v1; grid = 0; n = 0;
-        for (int s = 0; s < nseg; ++s) {
-            const long long g = (segs[s].rows + kTM * rt - 1) / (kTM * rt);
-            if (g == 0) continue;
-            int w, la, lh;
-            fits &= mlp2_shape(segs[s], w, la, lh);
-            maxw = std::max(maxw, w); m.lda = std::max(m.lda, la); m.ldh = std::max(m.ldh, lh);
-            m.seg[n] = segs[s];
-            m.seg[n].tstamp = g_mlp_tstamp;
-            m.role[n] = roles ? roles[s] : kRoleNone;
-            m.start[n] = grid;
-            grid += (int)g;
-            ++n;
-        }
-        if (rt == 1 || sizeof(float) * mlp2_lds_floats(rt, m.lda, m.ldh) <= (size_t)kLdsMax2) break;
-        rt >>= 1;
-    }
-    const auto record = [&](int kernel, int g, size_t lds) {
-        g_mlp_last_launch = MlpLaunch{kernel, rt, g, (int)lds};
+    const MlpPlan p = mlp_plan(segs, nseg, cus, mlp_switches());
+    const auto record = [&](int kernel, int grid, int lds) {
+        g_mlp_last_launch = MlpLaunch{kernel, p.rt, grid, lds};
         ++g_mlp_launches[kernel];
     };
-    if (n == 0) { record(kMlpNone, 0, 0); return hipSuccess; }
-    if (ro) m.ro = *ro;
-    m.nseg = n;
-    m.start[n] = grid;
-    const size_t lds2 = sizeof(float) * mlp2_lds_floats(rt, m.lda, m.ldh);
-    if (fits && lds2 <= (size_t)kLdsMax2) {
-        int kernel;
-        if (maxw > 128) {
-            // RT > 1: four waves of 64 columns each, one per SIMD (the 512-register budget of a lone wave holds the
-            // 4 x 4 accumulators and the 4 x 4 weight ring)
-            kernel = rt == 4 ? kMlp2_4_4_r4 : (rt == 2 ? kMlp2_4_4_r2 : kMlp2_8_2);
-            if (rt == 4) hipLaunchKernelGGL((k_mlp2<4, 4, false, 4>), dim3((unsigned)grid), dim3(256), lds2, st, m);
-            else if (rt == 2) hipLaunchKernelGGL((k_mlp2<4, 4, false, 2>), dim3((unsigned)grid), dim3(256), lds2, st, m);
-            else hipLaunchKernelGGL((k_mlp2<8, 2>), dim3((unsigned)grid), dim3(512), lds2, st, m);
-        } else if (nw4) {
-            kernel = kMlp2_4_2;
-            hipLaunchKernelGGL((k_mlp2<4, 2>), dim3((unsigned)grid), dim3(256), lds2, st, m);
-        } else if (n > 1 && rt == 1) {   // two workgroups per CU (128 registers)
-            kernel = kMlp2_8_1s;
-            hipLaunchKernelGGL((k_mlp2<8, 1, true>), dim3((unsigned)grid), dim3(512), lds2, st, m);
-        } else {
-            kernel = rt >= 2 ? kMlp2_8_1_r2 : kMlp2_8_1;
-            if (rt >= 2) hipLaunchKernelGGL((k_mlp2<8, 1, false, 2>), dim3((unsigned)grid), dim3(512), lds2, st, m);
-            else hipLaunchKernelGGL((k_mlp2<8, 1>), dim3((unsigned)grid), dim3(512), lds2, st, m);
-        }
-        record(kernel, grid, lds2);
-        return hipGetLastError();
+    if (p.n == 0) { record(kMlpNone, 0, 0); return hipSuccess; }
+    MlpMulti m;
+    std::memset(&m, 0, sizeof(m));
+    for (int i = 0; i < p.n; ++i) {
+        m.seg[i] = segs[p.src[i]];
+        m.seg[i].tstamp = g_mlp_tstamp;
+        m.role[i] = roles ? roles[p.src[i]] : kRoleNone;
     }
-    // the round-2 kernel, one launch per net (no rollout epilogues: callers check mlp_multi_fits first)
-    rt = 1;
-    for (int s = 0; s < n; ++s) {
-        if (m.role[s] != kRoleNone) return hipErrorInvalidValue;
-        const MlpArgs& a = m.seg[s];
-        const unsigned g = (unsigned)((a.rows + kTM - 1) / kTM);
-        int w = 0;
-        for (int i = 1; i <= a.layers; ++i) w = std::max(w, a.dims[i]);
-        if (w <= 128) hipLaunchKernelGGL((k_mlp<8, 1, 2>), dim3(g), dim3(512), mlp_lds_bytes(), st, a);
-        else if (wide4) hipLaunchKernelGGL((k_mlp<4, 4, 1>), dim3(g), dim3(256), mlp_lds_bytes(), st, a);
-        else hipLaunchKernelGGL((k_mlp<8, 2, 2>), dim3(g), dim3(512), mlp_lds_bytes(), st, a);
-        record(w <= 128 ? kMlp1_8_1_2 : (wide4 ? kMlp1_4_4_1 : kMlp1_8_2_2), (int)g, mlp_lds_bytes());
+    std::copy(p.start, p.start + 4, m.start);
+    m.nseg = p.n;
+    m.lda = p.lda;
+    m.ldh = p.ldh;
+    if (ro) m.ro = *ro;
+    // k_mlp2: one launch over all segments; k_mlp: one per net (no rollout epilogues: callers check mlp_multi_fits first)
+    for (int i = 0; i < (p.v2 ? 1 : p.n); ++i) {
+        if (p.kernel[i] == kMlpNone || (!p.v2 && m.role[i] != kRoleNone)) return hipErrorInvalidValue;
+        const int grid = p.v2 ? p.start[p.n] : p.grid[i];
+        void* arg = p.v2 ? static_cast<void*>(&m) : static_cast<void*>(&m.seg[i]);
+        (void)hipLaunchKernel(mlp_fn(p.kernel[i]), dim3((unsigned)grid), dim3(64u * kMlpTable[p.kernel[i]].nw), &arg,
+                              (size_t)p.lds, st);
+        record(p.kernel[i], grid, p.lds);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
