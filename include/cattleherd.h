@@ -405,6 +405,64 @@ typedef struct ch_marl_rollout_io {
 int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
                             const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream);
 
+/* ---- On-device policy evaluation ---------------------------------------------------------
+ * Replaces: stable_baselines3 evaluate_policy(model, env, n_eval_episodes, deterministic=True), as the CTDE driver
+ * runs it after training and EvalCallback runs it during training (CTDECattleHerder.py:139-148, 185): every env
+ * steps with the deterministic action until it has contributed its share of the n episodes; each counted episode's
+ * return and length (Monitor's info["episode"]) go into a list whose mean +- std is the model-selection signal.
+ * Here the list is a device table with `capacity` slots per env, filled by a recorder kernel after each step, so
+ * the evaluation runs without the host reading any per-step output.  CTDE handles only.  All arrays are
+ * caller-owned device memory.  (SB3 is not installed here: restated from its source, "parity unpinned".) */
+typedef struct ch_eval_table {
+    int32_t  capacity;      /* C: episode slots per env */
+    int32_t  _pad;
+    int32_t* quota;         /* device [E]: episodes env e still has to contribute in total (SB3's episode_count_targets) */
+    int32_t* count;         /* device [E]: episodes recorded for env e (never exceeds quota) */
+    double*  ep_return;     /* device [E][C]: io->episode_stats[e][0] of the recorded episode */
+    int32_t* ep_length;     /* device [E][C]: io->episode_stats[e][1] */
+    uint8_t* ep_flags;      /* device [E][C]: bit 0 terminated, bit 1 truncated (the step's outputs for env e) */
+    int32_t* ep_end_step;   /* device [E][C]: the evaluation step index at which it ended */
+    int64_t* remaining;     /* device [1]: sum over e of quota[e] - count[e] */
+} ch_eval_table;
+
+/* Start an evaluation of n_eval_episodes episodes: quota[e] = (n_eval_episodes + e) / E (evaluate_policy's
+ * episode_count_targets: the integer division leaves the later envs with one episode more), count = 0,
+ * remaining = n_eval_episodes.  The slots are not cleared: slot [e][k] is valid for k < count[e].
+ * CH_ERR_INVALID if n_eval_episodes < 1 or ceil(n_eval_episodes / E) > capacity; CH_ERR_UNSUPPORTED for a MARL
+ * handle. */
+int ch_eval_begin(ch_handle* h, const ch_eval_table* table, int32_t n_eval_episodes, void* stream);
+
+/* After a ch_step with CH_STEP_AUTORESET on the same stream (io->reset_happened and io->episode_stats are required,
+ * CH_ERR_INVALID otherwise): every env that ended an episode in that step (reset_happened[e] != 0) and is below its
+ * quota writes slot count[e] (return, length, the step's terminated / truncated, step_index), counts it and lowers
+ * `remaining`.  Episodes of an env at its quota are ignored, as evaluate_policy ignores them: the env keeps stepping.
+ * 0 <= step_index < 2^31. */
+int ch_eval_record(ch_handle* h, const ch_eval_table* table, const ch_step_io* io, int64_t step_index, void* stream);
+
+/* The evaluation loop in one call.  Per step t = 0, 1, ... on `stream`: ch_policy_forward(actor) on io->step->obs
+ * into io->mean; env_actions[e][i][c] = clamp(mean[e][4 i + c], -1, 1) for i < num_drones (predict's clip to the
+ * action Box and the env's read of the first num_drones rows; applied whether or not actor->clip is set, so a
+ * training actor evaluates unchanged; the actor's output must be at least 4 * num_drones wide); ch_step with
+ * auto-reset; ch_eval_record with step index first_step_index + t (run inside the next step's action kernel, while
+ * the step's outputs are still in place, and as a launch of its own before each read of `remaining`: three launches
+ * per step between reads).
+ * Every check_every steps (>= 1) and at max_steps (>= 1) `remaining` is copied to the host and the stream is
+ * synchronised -- nowhere else -- and the loop stops when it is 0.  Reaching max_steps with episodes outstanding is
+ * not an error: the call returns CH_OK with *remaining > 0.  *steps_run: the steps taken.  The steps after the last
+ * quota filled (at most check_every - 1) leave the table untouched -- recording is gated by the quotas -- and only
+ * advance the env state.  The call neither resets the envs nor begins the table (ch_reset, ch_eval_begin): a second
+ * call with first_step_index = the steps run so far continues an evaluation.
+ * A HIP error ends the loop at once (CH_ERR_DEVICE); the sticky device error word is read at every check and
+ * reported as ch_sync reports it. */
+typedef struct ch_eval_io {
+    const ch_step_io* step;   /* env step buffers: obs, reward, terminated, truncated, reset_happened, episode_stats */
+    float* mean;              /* scratch [E][actor->dims[last]] */
+    float* env_actions;       /* scratch [E][num_drones][4] */
+} ch_eval_io;
+int ch_evaluate_policy(ch_handle* h, const ch_mlp* actor, const ch_eval_table* table, const ch_eval_io* io,
+                       int64_t max_steps, int32_t check_every, int64_t first_step_index,
+                       int64_t* steps_run, int64_t* remaining, void* stream);
+
 /* ---- Native PPO minibatch update ---------------------------------------------------------------------------
  * Replaces: stable_baselines3 PPO.train for the CTDE driver's PPO("MlpPolicy", ...) (CTDECattleHerder.py:107-150),
  * one minibatch step at a time: ActorCriticPolicy.evaluate_actions (separate tanh MLPs obs -> pi -> action_net and

@@ -27,7 +27,10 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_spawn_table", "ch_mlp_forward", "ch_mlp_forward_masked", "ch_policy_forward", "ch_mlp_packed_size",
            "ch_mlp_pack", "ch_outputs_to_host", "ch_marl_rollout_collect", "ch_ppo_param_count", "ch_ppo_scratch_size",
            "ch_ppo_grad", "ch_ppo_adam", "ch_ppo_train", "ch_marl_ppo_param_count", "ch_marl_ppo_scratch_size",
-           "ch_marl_ppo_grad", "ch_marl_ppo_adam", "ch_marl_ppo_train")
+           "ch_marl_ppo_grad", "ch_marl_ppo_adam", "ch_marl_ppo_train", "ch_eval_begin", "ch_eval_record",
+           "ch_evaluate_policy")
+# the on-device evaluation's symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
+_EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -101,6 +104,17 @@ class ChMarlPpoData(ctypes.Structure):
                                                "value_targets")] + [("rows", ctypes.c_int64)]
 
 
+# the on-device evaluate_policy's structs (ch_eval_*; cattleherd/eval_policy.py)
+class ChEvalTable(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_int32), ("_pad", ctypes.c_int32)] + \
+        [(k, ctypes.c_void_p) for k in ("quota", "count", "ep_return", "ep_length", "ep_flags", "ep_end_step",
+                                        "remaining")]
+
+
+class ChEvalIO(ctypes.Structure):
+    _fields_ = [("step", ctypes.POINTER(ChStepIO)), ("mean", ctypes.c_void_p), ("env_actions", ctypes.c_void_p)]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -165,8 +179,12 @@ def lib():
         getattr(L, pre + "grad").argtypes = [N, H, D, vp, i64, vp, vp, vp, vp]
         getattr(L, pre + "adam").argtypes = [N, H, vp, vp, vp, vp, vp, vp]
         getattr(L, pre + "train").argtypes = [N, H, D, vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ch_evaluate_policy"):
+        L.ch_eval_begin.argtypes = [vp, P(ChEvalTable), i32, vp]
+        L.ch_eval_record.argtypes = [vp, P(ChEvalTable), P(ChStepIO), i64, vp]
+        L.ch_evaluate_policy.argtypes = [vp, P(ChMlp), P(ChEvalTable), P(ChEvalIO), i64, i32, i64, P(i64), P(i64), vp]
     for name in EXPORTS:
-        if name not in ("ch_last_error",) and (name != "ch_step_n" or hasattr(L, name)):
+        if name not in ("ch_last_error",) and (name not in ("ch_step_n",) + _EVAL_EXPORTS or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int
     L.ch_mlp_packed_size.restype = ctypes.c_int64
     L.ch_ppo_param_count.restype = L.ch_ppo_scratch_size.restype = ctypes.c_int64

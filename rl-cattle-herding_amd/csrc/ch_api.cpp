@@ -190,10 +190,14 @@ static void free_all(ch_handle* h) {
     for (void* p : {(void*)sg.count, (void*)sg.env, (void*)sg.stats, (void*)sg.obs})
         if (p) (void)hipFree(p);
     if (sg.count_host) (void)hipHostFree(sg.count_host);
+    if (h->eval_host) (void)hipHostFree(h->eval_host);
 }
 
-// the sticky device error word as a status (call after the stream has drained)
-static int device_status(ch_handle* h, int word) {
+}  // extern "C"
+
+// the sticky device error word as a status (call after the stream has drained; ch_handle.h: ch_api_eval.cpp reports
+// it too)
+int device_status(ch_handle* h, int word) {
     if (!word) return CH_OK;
     h->err_seen = true;
     return fail(h, CH_ERR_DEVICE,
@@ -202,6 +206,8 @@ static int device_status(ch_handle* h, int word) {
                                                   "the results of that step are wrong"
                                                 : ""));
 }
+
+extern "C" {
 
 int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** out) {
     if (!c || !out) return fail(nullptr, CH_ERR_INVALID, "ch_create: NULL argument");

@@ -1,5 +1,6 @@
-// ch_handle.h — the handle behind the C ABI, private to its two host files: ch_api.cpp (config, create / destroy, reset,
-// step, state, metrics, host output) and ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection).
+// ch_handle.h — the handle behind the C ABI, private to its host files: ch_api.cpp (config, create / destroy, reset,
+// step, state, metrics, host output), ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection) and
+// ch_api_eval.cpp (the on-device evaluate_policy).
 #pragma once
 #include <string>
 #include <vector>
@@ -88,6 +89,8 @@ struct ch_handle {
     std::vector<unsigned char> params_host;   // what d_params holds (uploaded again only when the parameters change)
     ch_rollout_state ro;
     ch_staging st;
+    // ch_evaluate_policy's pinned host copy of {the table's remaining, the device error word} (allocated on first use)
+    long long* eval_host = nullptr;
     // the device error word was reported to the caller (device_status) since it was last cleared
     bool err_seen = false;
     std::string err;
@@ -100,6 +103,9 @@ inline int fail(ch_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_err = msg;
     return code;
 }
+
+// the sticky device error word as a status, after the stream has drained (ch_api.cpp; what ch_sync returns)
+int device_status(ch_handle* h, int word);
 
 #define HIP_TRY(h, expr)                                                                           \
     do {                                                                                           \

@@ -230,6 +230,29 @@ hipError_t launch_stage_ended(long long E, const uint8_t* reset, const float* te
                               int blk_floats, long long* count, long long* env_out, double* stats_out, float* obs_out,
                               hipStream_t st);   // 0 store, 1 post, 2 gae, 3 apply (cap slots)
 
+// ch_eval.hip: the on-device evaluate_policy (ch_eval_*): the episode table's begin and recorder kernels and the
+// deterministic-action kernel of ch_evaluate_policy
+struct EvalArgs {
+    long long E;
+    int C;                     // episode slots per env
+    int step_index;
+    int *quota, *count;        // [E]
+    double* ep_return;         // [E][C]
+    int* ep_length;
+    uint8_t* ep_flags;
+    int* ep_end_step;
+    long long* remaining;      // [1]
+    const uint8_t* reset;      // the step's reset_happened [E]
+    const double* stats;       // the step's episode_stats [E][2]
+    const uint8_t *term, *trunc;   // the step's terminated / truncated [E] (CTDE: one column)
+};
+hipError_t launch_eval_begin(const EvalArgs& a, long long n_eval, hipStream_t st);
+hipError_t launch_eval_record(const EvalArgs& a, hipStream_t st);
+// env_actions[e][k] = clamp(mean[e * mean_ld + k], -1, 1) for k < act_w (= num_drones * 4 <= mean_ld; act_w >= 1);
+// record_prev (optional): first the recorder of the step before, in the same launch
+hipError_t launch_eval_actions(const float* mean, int mean_ld, int act_w, long long E, float* env_actions,
+                               const EvalArgs* record_prev, hipStream_t st);
+
 // up to three independent forwards in one launch (ch_policy.hip k_mlp2).  A segment's role folds the rollout
 // store into its last layer's epilogue (ch_rollout_collect): kRoleSample -- the actor's mean becomes the
 // Gaussian sample, its log-probability and the env actions (k_rollout_store's action half); kRoleValue -- the
