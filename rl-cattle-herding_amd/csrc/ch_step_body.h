@@ -1251,12 +1251,77 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
         const int g = QUAD ? dg : tid;
         const bool envl = QUAD ? dlane : g < Gv;
         const bool envw = envl && (!QUAD || dk == 0);
+
+        // ---- ahead of the cow items (H): every input of the reset decision that is final here.  The env scalars were
+        // staged before F_E, the drones' positions and per-drone terms are this wave's own, and the herd centroid is
+        // final at F_HC (written once per step); the herded count and the distance table are not.  What is left
+        // between H and R is the herded count, the terminated / truncated calls and the reset list.
+        //
+        // (The per-env bookkeeping as a whole: one env per lane, or per quad, in the reference's call order; the final
+        // scalars stay in the lane's registers from here and go to HBM in the write-back at the end of this wave's part.)
+        if constexpr (!QUAD) wave_sync();   // the drone lanes' nearest distances and flags, read by the env lanes
+        const int e = e0 + g, b0 = g * N;
+        if (envl) {
+            f_n = ei[I_N * G + g]; f_sc = ei[I_SC * G + g]; f_scA = ei[I_SCA * G + g]; f_hp = ei[I_HASPREV * G + g];
+            f_level = ei[I_LEVEL * G + g]; f_tally = ei[I_TALLY * G + g]; f_spawn = ei[I_SPAWN * G + g];
+            f_active = ei[I_ACTIVE * G + g]; f_episode = ei[I_EPISODE * G + g];
+            f_prev = S.prevd[g]; f_clock = S.clock[g];
+        }
+        int done = 0, rs = 0, n_term = 0, n_trunc = 0, n_nan = 0, level_r = f_level;
+        double ret = 0;
+        bool te2 = false, tr = false, time_up = false;
+        uint8_t any = 0;
+        PT cent = 0;   // HerdCentroid/DroneCentroid distance (f64 also in f32 mode; R(cent) where the f32 math reads it)
+        R eff = 0, ms = R(INFINITY), scx = 0, scy = 0;
+        const PT max_step_p = PT(0.3 * kMaxSpeedKmh * (1000.0 / 3600.0)) / PT(p.ctrl_freq);
+        // QUAD: the env's four drones' positions and terms on every lane of its quad (convergent DPP moves); here
+        // the ones the reset decision reads, the reward's after R
+        constexpr int NQ = QUAD ? 4 : 1;
+        R qpa[NQ];
+        {
+            PT qx[NQ], qy[NQ];
+            int qdf[NQ];
+            if constexpr (QUAD) {
+                PT x0 = 0, y0 = 0;
+                if (live) {
+                    if constexpr (MIX) { x0 = pd[0]; y0 = pd[1]; } else { x0 = PT(pos[0]); y0 = PT(pos[1]); }
+                }
+                qall(x0, qx); qall(y0, qy); qall(q_pa, qpa); qall(q_df, qdf);
+            }
+            if (envl && task) {
+                const int n = f_n;
+                PT sdx = 0, sdy = 0;
+                // per-drone sums without per-lane branches: a drone beyond NUM_DRONES adds +0, which leaves a sum
+                // that starts at +0 unchanged (x + +0 = x unless x = -0, and such a sum is never -0)
+                CH_UNROLL for (int i = 0; i < N; ++i) {
+                    const bool li = i < n;
+                    const PT xi = QUAD ? qx[i % NQ] : S.dxd[b0 + i], yi = QUAD ? qy[i % NQ] : S.dyd[b0 + i];
+                    sdx += li ? xi : PT(0); sdy += li ? yi : PT(0);
+                }
+                sdx = divc(sdx, PT(n)); sdy = divc(sdy, PT(n));
+                PT ex = sdx - S.hcxd[g], ey = sdy - S.hcyd[g];
+                cent = sqrt(ex * ex + ey * ey + PT(0) * PT(0));   // HerdCentroid/DroneCentroid, z = 0.95 both
+                bool anynan = false;
+                CH_UNROLL for (int i = 0; i < N; ++i) {
+                    const bool li = i < n;
+                    const R pa = QUAD ? qpa[i % NQ] : S.pa[b0 + i];
+                    const uint8_t df = li ? (QUAD ? (uint8_t)qdf[i % NQ] : S.dflags[b0 + i]) : 0;
+                    if (li && pa < ms) ms = pa;
+                    anynan |= (df & 8) != 0;
+                    any |= df;
+                }
+                if (anynan) ms = R(NAN);
+                time_up = (double)f_sc / p.ctrl_freq > p.episode_len;
+                if (g == 0) TS(32, (long long)clock64());
+            }
+        }
+        // (an empty asm that takes and returns both values: their chains end here, not sunk behind the wait)
+        asm volatile("" : "+v"(cent), "+v"(ms));
         lds_wait(fl + F_H, Gv * M + force, p.err);   // every cow item
         if (tid == 0) { TS(6, (long long)clock64()); PTS(3, (long long)clock64()); }
         if (live && task) {
-            if constexpr (QUAD) q_sc = cattle_term(S, tid, M, R(p.cs_cc));
-            else S.scat[tid] = cattle_term(S, tid, M, R(p.cs_cc));
             if constexpr (marl) {
+                S.scat[tid] = cattle_term(S, tid, M, R(p.cs_cc));
                 // MARLCattleAviary._computeReward's per-agent part at the step's starting level
                 // (MARLCattleAviary.py:110-178), on every drone lane at once: the prefix
                 // P = simple w_s + complex w_c + 0.1 w_surv (psp), Q = P + eff/100 w_eff + cattle w_cat --
@@ -1294,66 +1359,14 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 S.meor[tid] = marl_end_of_episode_L(Lv, lv, a, b, cent, eff, norm2(scx - pos[0], scy - pos[1]), n);
             }
         }
-        wave_sync();
+        if constexpr (marl) wave_sync();   // the drone lanes' prefixes
         if (tid == 0) TS(26, (long long)clock64());
 
-        // per-env bookkeeping, one env per lane, in the reference's call order; the final scalars stay in
-        // this lane's registers and go to HBM after the last barrier
-        const int e = e0 + g, b0 = g * N;
-        if (envl) {
-            f_n = ei[I_N * G + g]; f_sc = ei[I_SC * G + g]; f_scA = ei[I_SCA * G + g]; f_hp = ei[I_HASPREV * G + g];
-            f_level = ei[I_LEVEL * G + g]; f_tally = ei[I_TALLY * G + g]; f_spawn = ei[I_SPAWN * G + g];
-            f_active = ei[I_ACTIVE * G + g]; f_episode = ei[I_EPISODE * G + g];
-            f_prev = S.prevd[g]; f_clock = S.clock[g];
-        }
-        int done = 0, rs = 0, n_term = 0, n_trunc = 0, n_nan = 0, level_r = f_level;
-        double ret = 0;
-        bool te2 = false, tr = false;
-        PT cent = 0;   // HerdCentroid/DroneCentroid distance (f64 also in f32 mode; R(cent) where the f32 math reads it)
-        R eff = 0, ms = R(INFINITY), scx = 0, scy = 0;
-        const PT max_step_p = PT(0.3 * kMaxSpeedKmh * (1000.0 / 3600.0)) / PT(p.ctrl_freq);
-        // QUAD: the env's four drones' positions and terms on every lane of its quad (convergent DPP moves)
-        constexpr int NQ = QUAD ? 4 : 1;
-        PT qx[NQ], qy[NQ];
-        R qpa[NQ], qpb[NQ], qsa[NQ], qsb[NQ], qca[NQ], qcb[NQ], qps[NQ], qsc[NQ];
-        int qdf[NQ];
-        if constexpr (QUAD) {
-            PT x0 = 0, y0 = 0;
-            if (live) {
-                if constexpr (MIX) { x0 = pd[0]; y0 = pd[1]; } else { x0 = PT(pos[0]); y0 = PT(pos[1]); }
-            }
-            qall(x0, qx); qall(y0, qy); qall(q_pa, qpa); qall(q_pb, qpb); qall(q_df, qdf);
-            qall(q_sa, qsa); qall(q_sb, qsb); qall(q_ca, qca); qall(q_cb, qcb); qall(q_ps, qps); qall(q_sc, qsc);
-        }
         if (envl && task) {
             const int n = f_n;
-            PT sdx = 0, sdy = 0;
             const int herded = ei[I_HERD * G + g];   // counted by the cow waves (winding number)
             scx = S.hcx[g]; scy = S.hcy[g];          // herd centroid, summed by the cow waves
-            // per-drone sums without per-lane branches: a drone beyond NUM_DRONES adds +0, which leaves a sum
-            // that starts at +0 unchanged (x + +0 = x unless x = -0, and such a sum is never -0)
-            CH_UNROLL for (int i = 0; i < N; ++i) {
-                const bool li = i < n;
-                const PT xi = QUAD ? qx[i % NQ] : S.dxd[b0 + i], yi = QUAD ? qy[i % NQ] : S.dyd[b0 + i];
-                sdx += li ? xi : PT(0); sdy += li ? yi : PT(0);
-            }
-            sdx = divc(sdx, PT(n)); sdy = divc(sdy, PT(n));
-            PT ex = sdx - S.hcxd[g], ey = sdy - S.hcyd[g];
-            cent = sqrt(ex * ex + ey * ey + PT(0) * PT(0));   // HerdCentroid/DroneCentroid, z = 0.95 both
             eff = R((double)herded / M * 100);
-            bool anynan = false;
-            uint8_t any = 0;
-            CH_UNROLL for (int i = 0; i < N; ++i) {
-                const bool li = i < n;
-                const R pa = QUAD ? qpa[i % NQ] : S.pa[b0 + i];
-                const uint8_t df = li ? (QUAD ? (uint8_t)qdf[i % NQ] : S.dflags[b0 + i]) : 0;
-                if (li && pa < ms) ms = pa;
-                anynan |= (df & 8) != 0;
-                any |= df;
-            }
-            if (anynan) ms = R(NAN);
-            const bool time_up = (double)f_sc / p.ctrl_freq > p.episode_len;
-            if (g == 0) TS(32, (long long)clock64());
             if constexpr (!marl) {
                 // CattleAviary: _computeReward (CattleAviary.py:213-332), then _computeTerminated twice and
                 // _computeTruncated.  The terminated calls read nothing the reward writes (the reward uses the
@@ -1643,6 +1656,25 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             lds_signal(ps + V2Pipe<R>::P_N);
             if (tid == 0) PTS(5, (long long)clock64());
+        }
+        // ---- behind R (and P_N): the reward, which nothing before the books' write-back waits for.  CattleAviary's
+        // cattle term (closest cow, from the cow waves' distance table: untouched until the next step's cow items) and
+        // the rest of the per-drone terms are gathered here, off the path to the reset decision.
+        R qpb[NQ], qsa[NQ], qsb[NQ], qca[NQ], qcb[NQ], qps[NQ], qsc[NQ];
+        if constexpr (!marl) {
+            if (live && task) {
+                if constexpr (QUAD) q_sc = cattle_term(S, tid, M, R(p.cs_cc));
+                else S.scat[tid] = cattle_term(S, tid, M, R(p.cs_cc));
+            }
+            if constexpr (QUAD) {
+                // (pa a second time, from the drone's own register: two DPP moves per value, instead of four more
+                // doubles held across the H wait and the fast-reset block -- the pipelined instantiation sits at 161
+                // of the 168 VGPRs that three waves per SIMD allow)
+                qall(q_pa, qpa); qall(q_pb, qpb);
+                qall(q_sa, qsa); qall(q_sb, qsb); qall(q_ca, qca); qall(q_cb, qcb); qall(q_ps, qps); qall(q_sc, qsc);
+            } else {
+                wave_sync();   // the drone lanes' cattle terms, read by the env lanes
+            }
         }
         if (envl && task) {
             const int n = f_n;
