@@ -809,6 +809,17 @@ int ch_metrics(ch_handle* h, double* out, int32_t reset_after, void* stream) {
     return device_status(h, (int)h->mhost[CH_METRIC_COUNT]);
 }
 
+/* Internal (tests): the per-env metric rows [kMetricRows][E] as the step kernels keep them (the public sums' inputs and
+ * the two running rows of the open episode), copied to host memory after the stream's work. */
+int ch__metric_rows(ch_handle* h, double* host_out, void* stream) {
+    if (!h || !host_out) return fail(h, CH_ERR_INVALID, "ch__metric_rows: NULL argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpyAsync(host_out, h->metrics, sizeof(double) * kMetricRows * h->E, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return CH_OK;
+}
+
 int ch_metrics_device(ch_handle* h, double* dev_out, int32_t reset_after, void* stream) {
     if (!h || !dev_out) return fail(h, CH_ERR_INVALID, "ch_metrics_device: NULL argument");
     HIP_TRY(h, hipSetDevice(h->device));

@@ -167,7 +167,8 @@ __device__ __forceinline__ void cow_sync(int* f, int waves, bool global, int* er
 // (step2_body's PIPE instantiations write none of the slots above: its waves are in different steps at once.)  The
 // pipelined step loop's own stamps, 16 slots per step for the first 8 steps of a launch (slot 16 k + i), shader clock:
 //   drone wave of step k: 0 at the P_N wait (step 0: launch start), 1 chain start, 2 D published, 3 H received,
-//   4 R published, 5 P_N signalled, 6 books written back (P_B), 7 HW_ID
+//   4 R published, 5 P_N signalled, 6 env scalars written back (P_B), 7 books closed (P_K), with the wave's SIMD in
+//   bits 62-63
 //   cow waves: 8 first cow wave enters step k (at the P_B wait), 9 past P_B and P_C, 10 waits for D, 11 D seen,
 //   12 flock work done, waits for R (first cow wave), 13 the same, latest cow wave, 14 R seen (first cow wave),
 //   15 step end, latest cow wave
@@ -771,25 +772,63 @@ __device__ __forceinline__ void flock_combine(const StepParams<R>& p, V2Smem<R>&
 //   ho   [27][64]  per drone lane: the 26 state reals after the chain (a reset env: its new body) and evald's accumulator
 //   hoi  [2][64]   NUM_DRONES of the lane's env for the next step, the Philox step counter
 //   d1   [7][64]   the odd steps' copy of S.dx, dy, dz, dq (the even steps use the V2Layout arrays)
+//   met  [kMetricRows][16]  the metric rows of the workgroup's envs, owned by the books waves for the length of the
+//                  launch: staged from global memory by the cow waves in step 0 only (before F_E of step 0), then read,
+//                  updated and written back by the books wave of every step (which also stores them to global memory
+//                  every step).  The cow waves never touch them after step 0.
 //   flags1 [kV2Flags]  the odd steps' hand-off and work counters (the even steps: S.flags)
 //   sync           counters that run over the whole launch, never cleared inside it:
 //       P_N  = steps whose hand-off is final       (drone wave k -> drone wave k+1; target k+1)
-//       P_B  = steps whose books are written back  (drone wave k -> cow waves; target k+1)
+//       P_B  = steps whose env scalars are written back (drone wave k -> cow waves; target k+1).  It guards the global
+//              rows envi / envr / stale / obs_tag, which the cow waves load on entering step k+1, and the LDS rows they
+//              restage there (S.ei, S.prev, S.clock and the cow and pair tables): the books wave of step k reads none
+//              of them after this signal.  It does not say that the books are closed.
 //       P_C  = cow waves done with a step, summed  (cow waves among themselves; target W1 (k+1))
+//       P_K  = steps whose books are closed        (drone wave k -> cow waves and drone wave k+1; target k+1): the
+//              reward, term / trunc, metrics and episode records of step k are stored (released at workgroup scope) and
+//              that wave is done with S.dcow (the closest-cow search) and X.met.  The cow waves wait for it before the
+//              per-cow pass of step k+1, the first thing that overwrites S.dcow; the books wave of step k+1 waits for
+//              it before it touches X.met or stores to the rows above.
 //       P_SIMD + w = 1 + the SIMD of drone wave w
 // Invariant: step k uses counter set k & 1; that set is zero when step k's first signal can arrive (step 0 and 1: cleared
 // before the launch's only barrier; step k >= 2: cleared by the cow waves on entering step k-1, see phase 0).
+// S.LT and S.pl (the curriculum table and the pair list) are constant: staged once per launch (step2_pipe_init), so the
+// books wave may read LT whatever step the cow waves are in.
 template <class R>
 struct V2Pipe {
-    enum { P_N = 0, P_B, P_C, P_SIMD, P_COUNT = 8 };
-    static constexpr size_t kBytes = (27 + 7) * 64 * sizeof(R) + (2 * 64 + kV2Flags + P_COUNT) * sizeof(int);
+    enum { P_N = 0, P_B, P_C, P_SIMD, P_K = P_SIMD + 2, P_COUNT = 8 };
+    static_assert(P_K < P_COUNT, "launch-long counters");
+    static constexpr int kMetG = 16;   // envs per workgroup of the pipelined instantiation
+    static constexpr size_t kBytes = (27 + 7) * 64 * sizeof(R) + (size_t)kMetricRows * kMetG * sizeof(double) +
+                                     (2 * 64 + kV2Flags + P_COUNT) * sizeof(int);
     R *ho, *d1;
+    double* met;
     int *hoi, *flags1, *sync;
     __device__ explicit V2Pipe(unsigned char* base) {
         ho = (R*)base; d1 = ho + 27 * 64;
-        hoi = (int*)(d1 + 7 * 64); flags1 = hoi + 2 * 64; sync = flags1 + kV2Flags;
+        met = (double*)(d1 + 7 * 64);
+        hoi = (int*)(met + kMetricRows * kMetG); flags1 = hoi + 2 * 64; sync = flags1 + kV2Flags;
     }
 };
+
+// ---- env scalars back to HBM from the env lanes' registers (nothing after this step reads them).  A macro, expanded
+// at one of two places in step2_body: at its end, or (PIPE) ahead of the reward; it reads step2_body's locals (the f_*
+// scalars, stepi / stepi_env, envw, e0, dg, E, wobs, p) and is undefined again right behind that function.
+#define CH_ENV_WRITE_BACK() do { \
+        if (QUAD ? envw : tid < Gv) {                                                                                    \
+            const int e = e0 + (QUAD ? dg : tid);                                                                        \
+            CH_STS(&p.envi[0 * E + e], f_n); CH_STS(&p.envi[1 * E + e], f_sc); CH_STS(&p.envi[2 * E + e], f_scA);        \
+            CH_STS(&p.envi[3 * E + e], f_hp); CH_STS(&p.envi[4 * E + e], f_level); CH_STS(&p.envi[5 * E + e], f_tally);  \
+            CH_STS(&p.envi[6 * E + e], f_spawn); CH_STS(&p.envi[7 * E + e], f_active); CH_STS(&p.envi[8 * E + e], f_episode); \
+            CH_STS(&p.envi[9 * E + e], (QUAD ? stepi : stepi_env) + 1);   /* ch_step calls on this env */                    \
+            CH_STS(&p.envr[0 * E + e], R(f_prev)); CH_STS(&p.envr[1 * E + e], f_clock);                                  \
+            if constexpr (MIX) CH_STS(&p.prev64[e], f_prev);                                                             \
+            /* this step wrote the env's Euler cache and, unless obs were masked off, its whole obs block */                 \
+            p.stale[e] = 0;                                                                                              \
+            if (wobs) p.stale[E + e] = 0;                                                                                \
+            p.obs_tag[e] = wobs ? (unsigned long long)(uintptr_t)p.obs : 0ull;                                           \
+        }                                                                                                                \
+    } while (0)
 
 // GT/NT/MT > 0 specialise the kernel for one geometry (envs per workgroup, drones, cattle): the LDS
 // carve and all index arithmetic then fold to immediates, which keeps the kernel within the SGPR file.
@@ -812,6 +851,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
     constexpr bool PIPE = ROLE != 0;
     static_assert(!PIPE || (sizeof(R) == 8 && MODE == 0 && GT == 16 && NT == 4 && !PW && !TOBS && !PHYS),
                   "the pipelined step loop is the configs[3] f64 instantiation's");
+    static_assert(!PIPE || GT == V2Pipe<R>::kMetG, "X.met holds kMetG envs per metric row");
     constexpr bool marl = MODE == 1;
     // f32 mode: positions, centroids and the approach delta in f64 (StepParams::pos64); PT = their type
     constexpr bool MIX = sizeof(R) == 4;
@@ -885,22 +925,28 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
     uint8_t stale_o = 0;        // cow waves' env lanes: the obs block flag and the buffer tag, combined after the barrier
     unsigned long long tag_o = 0;
     if constexpr (PIPE) {
-        if (ROLE == 1 && tid == 0) { PTS(0, (long long)clock64()); PTS(7, (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4)); }
+        if (ROLE == 1 && tid == 0) PTS(0, (long long)clock64());
         if (ROLE == 2 && ct == 0) PTS(8, (long long)clock64());
         if (kstep > 0) {
             if (ROLE == 2) {
-                // (a) step k's loads come after step k-1's stores: the books wave's write-back (P_B, released at
-                // workgroup scope by that wave) and every cow wave's final pass (P_C, a cow-wave barrier that publishes
-                // their global stores).  (c) the outputs of step k are ordered after those of step k-1 through the
-                // same chain: the books of step k wait for this step's cow items (F_H).
+                // (a) step k's loads come after step k-1's stores: the books wave's write-back of the env scalars
+                // (envi, envr, stale, obs_tag: P_B, released at workgroup scope by that wave, which reads none of the
+                // LDS rows restaged below after it) and every cow wave's final pass (P_C, a cow-wave barrier that
+                // publishes their global stores).  The books of step k-1 may still be open here: their wave reads
+                // only its registers, the constant S.LT, X.met (never touched by the cow waves after step 0) and
+                // S.dcow, which this step overwrites only behind the P_K wait ahead of the per-cow pass.  (c) the
+                // outputs of step k are ordered after those of step k-1 through P_K: that wait precedes this step's
+                // cow items (F_H), which the books of step k wait for, and the books wave of step k waits for P_K
+                // itself before its output stores.
                 lds_wait(ps + V2Pipe<R>::P_B, kstep, p.err);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 lds_signal(ps + V2Pipe<R>::P_C);
                 lds_wait(ps + V2Pipe<R>::P_C, W1 * kstep, p.err);
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 // (b) the counters of step k-1 are cleared for step k+1 once every wave is done with them: the cow
-                // waves by P_C, the books wave by P_B.  Step k+1's drone wave touches them only after R_k, which
-                // follows this step's F_E and F_H, which follow this clear.
+                // waves by P_C, the books wave by P_B (behind it that wave signals only P_K, a launch-long counter).
+                // Step k+1's drone wave touches them only after R_k, which follows this step's F_E and F_H, which
+                // follow this clear.
                 int* const flp = (kstep & 1) ? flags0 : X.flags1;
                 if (ct < kV2Flags) flp[ct] = 0;
             } else {
@@ -927,8 +973,12 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             tag_o = p.obs_tag[e];
             er0[0] = p.envr[e]; er0[1] = p.envr[E + e];
             if constexpr (MIX) prev0d = p.prev64[e];
+            // (PIPE: the metric rows are read from global memory in a launch's step 0 only; from then on they stay
+            // with the books waves in X.met)
+            if (!PIPE || kstep == 0) {
 #pragma unroll
-            for (int r = 0; r < kMetricRows; ++r) met0[r] = p.metrics[r * E + e];
+                for (int r = 0; r < kMetricRows; ++r) met0[r] = p.metrics[r * E + e];
+            }
         }
     } else if (PIPE && kstep > 0) {
         // the chain state from the previous step's drone wave, through LDS (global memory holds the same values)
@@ -1013,9 +1063,11 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             CH_STS(&p.cattle[0 * CS + ci], x); CH_STS(&p.cattle[1 * CS + ci], y);
             S.cx[u] = x; S.cy[u] = y; S.cvx[u] = vx; S.cvy[u] = vy;
         }
-        for (int k = ct; k < (int)(sizeof(kLevels) / 4); k += CW)
-            reinterpret_cast<uint32_t*>(S.LT)[k] = reinterpret_cast<const uint32_t*>(kLevels)[k];
-        for (int k = ct; k < P; k += CW) const_cast<uint16_t*>(S.pl)[k] = p.pairs[k];
+        if constexpr (!PIPE) {   // (PIPE: the two constant tables are staged once per launch, step2_pipe_init)
+            for (int k = ct; k < (int)(sizeof(kLevels) / 4); k += CW)
+                reinterpret_cast<uint32_t*>(S.LT)[k] = reinterpret_cast<const uint32_t*>(kLevels)[k];
+            for (int k = ct; k < P; k += CW) const_cast<uint16_t*>(S.pl)[k] = p.pairs[k];
+        }
         for (int k = ct; k < G * M; k += CW) {
             S.nbm[k] = 0;
             if (sep) S.cnt[k] = 0;
@@ -1037,8 +1089,16 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             ei[I_OBSD * G + g] = ei0[9];   // the obs block's constant bytes are unknown
             S.prev[g] = er0[0]; S.clock[g] = er0[1];
             if constexpr (MIX) S.prevd[g] = prev0d;
+            if constexpr (PIPE) {
+                // step 0 of the launch: straight into the books waves' rows (published by F_E of step 0)
+                if (kstep == 0) {
 #pragma unroll
-            for (int r = 0; r < kMetricRows; ++r) S.met[r * G + g] = met0[r];
+                    for (int r = 0; r < kMetricRows; ++r) X.met[r * G + g] = met0[r];
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < kMetricRows; ++r) S.met[r * G + g] = met0[r];
+            }
         }
         // compact list of flocking envs (BaseAviary.py:454: every second step_counter_A)
         const unsigned long long bal = __ballot(flk);
@@ -1657,9 +1717,31 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             lds_signal(ps + V2Pipe<R>::P_N);
             if (tid == 0) PTS(5, (long long)clock64());
         }
-        // ---- behind R (and P_N): the reward, which nothing before the books' write-back waits for.  CattleAviary's
-        // cattle term (closest cow, from the cow waves' distance table: untouched until the next step's cow items) and
-        // the rest of the per-drone terms are gathered here, off the path to the reset decision.
+        // PIPE: the reward's inputs among the env scalars (the early write-back below moves f_* on to their final values)
+        int r_n = 0, r_hp = 0;
+        PT r_prev = 0;
+        if constexpr (PIPE) { r_n = f_n; r_hp = f_hp; r_prev = f_prev; }
+        if constexpr (PIPE) {
+            // Every value of the write-back is final at R: the scalar updates the reward block makes in the other
+            // instantiations are applied here, in its order and under its conditions (the reward reads r_n, r_hp and
+            // r_prev instead), and the env scalars go back ahead of the reward.
+            if (envl && task) {
+                f_prev = cent; f_hp = 1;
+                f_sc += p.substeps;
+                if (rs) reset_scalars(p, e, f_n, f_sc, f_scA, f_spawn, f_episode, f_active, f_hp, f_prev, f_clock, n_next);
+            }
+            CH_ENV_WRITE_BACK();
+            // P_B: the env scalars of step k are written back (released at workgroup scope) and this wave reads none
+            // of S.ei, S.prev, S.clock or the cow tables any more: the cow waves may load step k+1's env scalars and
+            // restage those rows.  The books stay open (see P_K).
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            lds_signal(ps + V2Pipe<R>::P_B);
+            if (tid == 0) PTS(6, (long long)clock64());
+        }
+        // ---- behind R (and P_N; PIPE: and P_B): the reward, which nothing before the books' close waits for.
+        // CattleAviary's cattle term (closest cow, from the cow waves' distance table: untouched until the next step's
+        // cow items; PIPE: until those waves have seen P_K) and the rest of the per-drone terms are gathered here, off
+        // the path to the reset decision.
         R qpb[NQ], qsa[NQ], qsb[NQ], qca[NQ], qcb[NQ], qps[NQ], qsc[NQ];
         if constexpr (!marl) {
             if (live && task) {
@@ -1676,8 +1758,17 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 wave_sync();   // the drone lanes' cattle terms, read by the env lanes
             }
         }
+        if constexpr (PIPE) {
+            // P_K of step k-1: the other drone wave has closed its books.  It stored to the addresses this wave stores
+            // to below (reward, term, trunc, metrics, episode records) and owned X.met until then.  (Expected never
+            // to spin: those books closed a whole chain ago.)
+            if (kstep > 0) {
+                lds_wait(ps + V2Pipe<R>::P_K, kstep, p.err);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+        }
         if (envl && task) {
-            const int n = f_n;
+            const int n = PIPE ? r_n : f_n;
             if constexpr (!marl) {
                 const Level& Lv = LT[level_r];
                 // branch-free per-drone sums (a skipped term adds +0, see the centroid above)
@@ -1697,8 +1788,9 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 const R n2 = R(n * 2.0), nn = R(n);
                 sp_complex = divc(sp_complex, n2); sp_simple = divc(sp_simple, n2);
                 R approach = 0;
-                if (f_hp) approach = R(clip(divc(f_prev - cent, max_step_p + PT(1e-6)) * PT(5), PT(-1.0), PT(1.0)));
-                f_prev = cent; f_hp = 1;
+                if (PIPE ? r_hp : f_hp)
+                    approach = R(clip(divc((PIPE ? r_prev : f_prev) - cent, max_step_p + PT(1e-6)) * PT(5), PT(-1.0), PT(1.0)));
+                if constexpr (!PIPE) { f_prev = cent; f_hp = 1; }
                 CH_UNROLL for (int i = 0; i < N; ++i) cat += i < n ? scat_i[i] : R(0);
                 cat = divc(cat, nn);
                 R rg = sp_simple * R(Lv.w_simple) + sp_complex * R(Lv.w_complex) + R(0.1) * R(Lv.w_survival) +
@@ -1716,9 +1808,12 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 n_term = te2; n_trunc = tr; n_nan = rew != rew;
             }
             if (g == 0) TS(19, (long long)clock64());
-            f_sc += marl ? 1 : p.substeps;
-            // metric accumulators (rank-local; bench.py all-reduces them)
-            const double* mt = S.met;
+            if constexpr (!PIPE) f_sc += marl ? 1 : p.substeps;
+            // metric accumulators (rank-local; bench.py all-reduces them).  PIPE: the rows live in X.met for the length
+            // of the launch (this wave owns them between P_K of step k-1 and its own P_K); global memory gets every
+            // step's values all the same.
+            double* mt = S.met;
+            if constexpr (PIPE) mt = X.met;
             double o[kMetricRows];
 #pragma unroll
             for (int r = 0; r < kMetricRows; ++r) o[r] = mt[r * G + g];
@@ -1743,37 +1838,32 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             }
 #pragma unroll
             for (int r = 0; r < kMetricRows; ++r)
-                if (envw) CH_STS(&p.metrics[r * E + e], o[r]);
+                if (envw) {
+                    CH_STS(&p.metrics[r * E + e], o[r]);
+                    if constexpr (PIPE) mt[r * G + g] = o[r];
+                }
             if (g == 0) TS(28, (long long)clock64());
             if (p.reset_happened && envw) p.reset_happened[e] = rs;
             // SB3 auto-reset: the new episode's scalars (the cow waves rebuild its bodies and observation)
-            if (rs) reset_scalars(p, e, f_n, f_sc, f_scA, f_spawn, f_episode, f_active, f_hp, f_prev, f_clock, n_next);
+            if constexpr (!PIPE) {
+                if (rs) reset_scalars(p, e, f_n, f_sc, f_scA, f_spawn, f_episode, f_active, f_hp, f_prev, f_clock, n_next);
+            }
             if (p.agent_active && envw)
                 for (int i = 0; i < N; ++i) p.agent_active[(long long)e * N + i] = (f_active >> i) & 1;
         } else if (envw && p.reset_happened) {
             p.reset_happened[e] = 0;
         }
         if (tid == 0) TS(7, (long long)clock64());
-        // ---- env scalars back to HBM from the env lanes' registers (nothing after this step reads them)
-        if (QUAD ? envw : tid < Gv) {
-            const int e = e0 + (QUAD ? dg : tid);
-            CH_STS(&p.envi[0 * E + e], f_n); CH_STS(&p.envi[1 * E + e], f_sc); CH_STS(&p.envi[2 * E + e], f_scA);
-            CH_STS(&p.envi[3 * E + e], f_hp); CH_STS(&p.envi[4 * E + e], f_level); CH_STS(&p.envi[5 * E + e], f_tally);
-            CH_STS(&p.envi[6 * E + e], f_spawn); CH_STS(&p.envi[7 * E + e], f_active); CH_STS(&p.envi[8 * E + e], f_episode);
-            CH_STS(&p.envi[9 * E + e], (QUAD ? stepi : stepi_env) + 1);   // ch_step calls on this env
-            CH_STS(&p.envr[0 * E + e], R(f_prev)); CH_STS(&p.envr[1 * E + e], f_clock);
-            if constexpr (MIX) CH_STS(&p.prev64[e], f_prev);
-            // this step wrote the env's Euler cache and, unless obs were masked off, its whole obs block
-            p.stale[e] = 0;
-            if (wobs) p.stale[E + e] = 0;
-            p.obs_tag[e] = wobs ? (unsigned long long)(uintptr_t)p.obs : 0ull;
-        }
         if constexpr (PIPE) {
-            // P_B: the books of step k are closed and written back (released at workgroup scope): the cow waves may
-            // load step k+1's env scalars and restage the LDS rows this wave read
+            // P_K: the books of step k are closed -- every output store of this step is released at workgroup scope,
+            // X.met holds the step's rows and this wave is done with S.dcow.
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            lds_signal(ps + V2Pipe<R>::P_B);
-            if (tid == 0) PTS(6, (long long)clock64());
+            lds_signal(ps + V2Pipe<R>::P_K);
+            if (tid == 0)
+                PTS(7, (long long)((unsigned long long)clock64() & ((1ull << 62) - 1)) |
+                           (long long)((unsigned long long)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3) << 62));
+        } else {
+            CH_ENV_WRITE_BACK();
         }
     } else {
         // ============ cow waves ================================================================
@@ -1930,6 +2020,16 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
         if (ct == 0) { TS(8, (long long)clock64()); PTS(10, (long long)clock64()); }
         lds_wait(fl + F_D, 1, p.err);
         if (ct == 0) { TS(9, (long long)clock64()); PTS(11, (long long)clock64()); }
+        if constexpr (PIPE) {
+            // P_K: the books of step k-1 are closed.  The pass below is the first thing in this step that overwrites
+            // S.dcow, which that books wave's closest-cow search reads; and since F_H of this step is signalled behind
+            // this wait, every output store of the books of step k follows those of step k-1.  (Expected never to
+            // spin: the books close within a fraction of a step.)
+            if (kstep > 0) {
+                lds_wait(ps + V2Pipe<R>::P_K, kstep, p.err);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+        }
         skip_now = skip_post;
         for (;;) {   // per cow: distances, winding number, observation entries (the herd centroid is done)
             const int b = grab(fl + C_COWS, 64, skip_post), u = b + lane;
@@ -2268,9 +2368,10 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
     }
 }
 
+#undef CH_ENV_WRITE_BACK
 
 // Once per launch of the pipelined step loop, by every wave: both counter sets and the launch-long counters cleared, the
-// two drone waves' SIMDs recorded, then the launch's only workgroup barrier.
+// two drone waves' SIMDs recorded, the two constant tables staged, then the launch's only workgroup barrier.
 template <class R, int MODE, int GT, int NT, int MT>
 __device__ __forceinline__ void step2_pipe_init(const StepParams<R>& p) {
     extern __shared__ __align__(16) unsigned char smem_[];
@@ -2279,9 +2380,14 @@ __device__ __forceinline__ void step2_pipe_init(const StepParams<R>& p) {
     const V2Pipe<R> X(smem_ + L.bytes());
     const int t = threadIdx.x;
     if (t < kV2Flags) { S.flags[t] = 0; X.flags1[t] = 0; }
-    if (t < V2Pipe<R>::P_SIMD) X.sync[t] = 0;
+    if (t < V2Pipe<R>::P_SIMD || t == V2Pipe<R>::P_K) X.sync[t] = 0;
     if ((t & 63) == 0 && t < 128)
         X.sync[V2Pipe<R>::P_SIMD + (t >> 6)] = 1 + (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3);
+    // the constant tables (curriculum levels, pair list): the books wave reads LT while the cow waves are a step ahead,
+    // so no step rewrites them
+    for (int k = t; k < (int)(sizeof(kLevels) / 4); k += (int)blockDim.x)
+        reinterpret_cast<uint32_t*>(S.LT)[k] = reinterpret_cast<const uint32_t*>(kLevels)[k];
+    for (int k = t; k < MT * (MT - 1) / 2; k += (int)blockDim.x) const_cast<uint16_t*>(S.pl)[k] = p.pairs[k];
     lds_barrier();
 }
 

@@ -165,8 +165,9 @@ def trace(mode, E, n, m, prec, G=None, B=None, steps=4, summary=None):
 def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
     """The pipelined step loop of k_step2_multi (configs[3] f64: two drone waves that alternate steps): ch_step_n
     launches of 8 steps, stamped per step (ch_step_body.h PTS: slot 16 k + i).  Per step k = 2..7, medians over the
-    workgroups, in cycles: R_{k-1} -> chain start k, the chain, D -> H, H -> R, R -> books written back, the period
-    R_{k-1} -> R_k; when the cow waves enter step k and how long they wait for the books of step k-1, for D_k and R_k."""
+    workgroups, in cycles: R_{k-1} -> chain start k, the chain, D -> H, H -> R, R -> P_B (env scalars written back), R ->
+    books closed (P_K), the period R_{k-1} -> R_k; when the cow waves enter step k, how long they wait for P_B and P_C
+    of step k-1 ("cow waves in"), for D_k and R_k."""
     L = _lib.lib()
     b = HerdBatch(E, n, m, mode=mode, precision=prec)
     if G is not None:
@@ -191,17 +192,22 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
             print("   no per-step stamps: this library's kernel is not the pipelined one")
             b.close()
             return False
-        simd = (t[:, :2, 7] >> 4) & 3
+        # slot 7: books closed (P_K) in bits 0-61, the drone wave's SIMD in bits 62-63; a library from before P_K
+        # stamps the HW_ID register there (SIMD in bits 4-5) and closes its books at P_B
+        has_pk = bool((t[:, :, 7] >> 62 != 0).any() or (t[:, :, 7] > (1 << 32)).all())
+        simd = ((t[:, :2, 7] >> 62) & 3) if has_pk else ((t[:, :2, 7] >> 4) & 3)
+        pk = (t[:, :, 7] & ((1 << 62) - 1)) if has_pk else t[:, :, 6]
         print(f" launch {s}: drone waves on different SIMDs in {int((simd[:, 0] != simd[:, 1]).sum())} of {grid} workgroups")
         rows = []
         for k in range(2, 8):
             R0, c = t[:, k - 1, 4], t[:, k]
             r = {"R_to_chain_start": q50(c[:, 1] - R0), "drone_waits_PN": q50(c[:, 1] - c[:, 0]),
                  "chain": q50(c[:, 2] - c[:, 1]), "D_to_H": q50(c[:, 3] - c[:, 2]), "H_to_R": q50(c[:, 4] - c[:, 3]),
-                 "R_to_PN": q50(c[:, 5] - c[:, 4]), "R_to_books_done": q50(c[:, 6] - c[:, 4]),
+                 "R_to_PN": q50(c[:, 5] - c[:, 4]), "R_to_PB": q50(c[:, 6] - c[:, 4]),
+                 "R_to_books_closed": q50(pk[:, k] - c[:, 4]),
                  "period_R_to_R": q50(c[:, 4] - R0),
-                 "cow_entry_after_R": q50(c[:, 8] - R0), "cow_waits_books": q50(c[:, 9] - c[:, 8]),
-                 "cow_start_after_R": q50(c[:, 9] - R0), "cow_ready_for_D_after_R": q50(c[:, 10] - R0),
+                 "cow_entry_after_R": q50(c[:, 8] - R0), "cow_waits_PB_PC": q50(c[:, 9] - c[:, 8]),
+                 "cow_waves_in_after_R": q50(c[:, 9] - R0), "cow_ready_for_D_after_R": q50(c[:, 10] - R0),
                  "cow_waits_D": q50(c[:, 11] - c[:, 10]), "D_after_R": q50(c[:, 2] - R0),
                  "cow_flock_done_after_D": q50(c[:, 12] - c[:, 11]), "last_cow_flock_done_after_D": q50(c[:, 13] - c[:, 11]),
                  "cow_waits_R": q50(c[:, 14] - c[:, 12]), "cow_end_after_R_k": q50(c[:, 15] - c[:, 4]),
@@ -214,7 +220,8 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
             summary.append({"wg_cycles_q50": mean["period_R_to_R"], "chain_cycles_q50": mean["chain"],
                             "chain_start": mean["R_to_chain_start"], "chain_done": mean["D_after_R"],
                             "h_received": mean["D_after_R"] + mean["D_to_H"], "reset_list": mean["period_R_to_R"],
-                            "books_done_after_R": mean["R_to_books_done"], "cow_start_after_R": mean["cow_start_after_R"],
+                            "books_done_after_R": mean["R_to_books_closed"], "pb_after_R": mean["R_to_PB"],
+                            "cow_start_after_R": mean["cow_waves_in_after_R"],
                             "cow_waits_D": mean["cow_waits_D"], "cow_waits_R": mean["cow_waits_R"],
                             "origin": "R of the previous step (pipelined loop)"})
     b.close()
