@@ -202,7 +202,7 @@ int device_status(ch_handle* h, int word) {
     h->err_seen = true;
     return fail(h, CH_ERR_DEVICE,
                 "device error word " + std::to_string(word) +
-                    ((word & CH_DEVERR_HANDOFF) ? ": a step kernel's LDS hand-off timed out (ch_step_body.h lds_wait); "
+                    ((word & CH_DEVERR_HANDOFF) ? ": a step kernel's LDS hand-off timed out (ch_step_sync.h lds_wait); "
                                                   "the results of that step are wrong"
                                                 : ""));
 }

@@ -96,16 +96,16 @@ __device__ __forceinline__ void reset_drone_store(const StepParams<R>& p, long l
     const long long DS = (long long)p.E * p.NC;
     R* D = p.drone;
     if (p.evald) p.evald[di] = 0;   // episode_drone_distances: (0, 0) -- _housekeeping zeroes self.pos (BaseAviary.py:567, 683-688)
-    D[0 * DS + di] = R(x); D[1 * DS + di] = R(y); D[2 * DS + di] = R(z);
+    D[kRowPos * DS + di] = R(x); D[(kRowPos + 1) * DS + di] = R(y); D[(kRowPos + 2) * DS + di] = R(z);
     if (p.pos64) { p.pos64[0 * DS + di] = x; p.pos64[1 * DS + di] = y; p.pos64[2 * DS + di] = z; }
-    D[3 * DS + di] = 0; D[4 * DS + di] = 0; D[5 * DS + di] = 0; D[6 * DS + di] = 1;
+    D[kRowQuat * DS + di] = 0; D[(kRowQuat + 1) * DS + di] = 0; D[(kRowQuat + 2) * DS + di] = 0; D[(kRowQuat + 3) * DS + di] = 1;
     // loadURDF: the links' cached transforms at the spawn attitude
-    D[22 * DS + di] = 0; D[23 * DS + di] = 0; D[24 * DS + di] = 0; D[25 * DS + di] = 1;
+    D[kRowLink * DS + di] = 0; D[(kRowLink + 1) * DS + di] = 0; D[(kRowLink + 2) * DS + di] = 0; D[(kRowLink + 3) * DS + di] = 1;
 #pragma unroll
-    for (int c = 7; c < 13; ++c) D[c * DS + di] = 0;
+    for (int c = kRowVel; c < kRowPid; ++c) D[c * DS + di] = 0;   // linear and angular velocity
     if (!p.compat) {
 #pragma unroll
-        for (int c = 13; c < 22; ++c) D[c * DS + di] = 0;
+        for (int c = kRowPid; c < kRowLink; ++c) D[c * DS + di] = 0;
     }
 }
 

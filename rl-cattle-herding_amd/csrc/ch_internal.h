@@ -11,6 +11,9 @@ namespace ch {
 constexpr int kNMax = 12;          // GLOBAL_MAX_NUM_DRONES (BaseAviary.py:112)
 constexpr int kMMax = 64;          // cattle per env supported by the team mapping (TEAM <= 64)
 constexpr int kDroneComps = 26;    // px py pz qx qy qz qw vx vy vz wx wy wz pid[9] qlag[4] (cached link frame)
+// first row of each part of a drone's state in the SoA arrays (component c of a part: row + c); kRowEvalDist is the extra
+// row of the pipelined step loop's LDS hand-off (update_evaluation_metrics' accumulator), not a row of the state
+enum { kRowPos = 0, kRowQuat = 3, kRowVel = 7, kRowOmega = 10, kRowPid = 13, kRowLink = 22, kRowEvalDist = kDroneComps };
 constexpr int kCattleComps = 4;    // x y vx vy
 constexpr int kPhysComps = 7;      // last_clipped_action[4] (drag input), DYN rpy_rates[3]
 constexpr int kEnvReal = 2;        // prev_cent, clock
@@ -81,7 +84,7 @@ struct StepParams {
 };
 
 // device error word bits (ch_api.cpp reports them as CH_ERR_DEVICE)
-constexpr int CH_DEVERR_HANDOFF = 1;       // a v2 LDS hand-off wait ran out of spins (ch_step_body.h lds_wait)
+constexpr int CH_DEVERR_HANDOFF = 1;       // a v2 LDS hand-off wait ran out of spins (ch_step_sync.h lds_wait)
 // diagnostics phase_mask bits beyond 1/2/4/8 (skip drones / flock / task / obs)
 constexpr int CH_PHASE_FORCE_TIMEOUT = 64; // test only: the drone wave waits for a hand-off that never comes
 

@@ -183,21 +183,22 @@ __global__ __launch_bounds__(64) void k_env(StepParams<R> p) {
         // ---- phase 1: drones (lane k) and cattle (lane j) ----------------------------------------
         if (valid && t < n) {
             const long long di = (long long)e * p.NC + t;
-            R pos[3] = {ld(p.drone, 0, DS, di), ld(p.drone, 1, DS, di), ld(p.drone, 2, DS, di)};
+            R pos[3] = {ld(p.drone, kRowPos, DS, di), ld(p.drone, kRowPos + 1, DS, di), ld(p.drone, kRowPos + 2, DS, di)};
             double pd[3] = {0, 0, 0};
             if constexpr (MIX) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) { pd[c] = p.pos64[c * DS + di]; pos[c] = R(pd[c]); }
             }
             const R px0 = pos[0], py0 = pos[1];
-            R q[4] = {ld(p.drone, 3, DS, di), ld(p.drone, 4, DS, di), ld(p.drone, 5, DS, di), ld(p.drone, 6, DS, di)};
-            R v[3] = {ld(p.drone, 7, DS, di), ld(p.drone, 8, DS, di), ld(p.drone, 9, DS, di)};
-            R w[3] = {ld(p.drone, 10, DS, di), ld(p.drone, 11, DS, di), ld(p.drone, 12, DS, di)};
+            R q[4] = {ld(p.drone, kRowQuat, DS, di), ld(p.drone, kRowQuat + 1, DS, di), ld(p.drone, kRowQuat + 2, DS, di),
+                      ld(p.drone, kRowQuat + 3, DS, di)};
+            R v[3] = {ld(p.drone, kRowVel, DS, di), ld(p.drone, kRowVel + 1, DS, di), ld(p.drone, kRowVel + 2, DS, di)};
+            R w[3] = {ld(p.drone, kRowOmega, DS, di), ld(p.drone, kRowOmega + 1, DS, di), ld(p.drone, kRowOmega + 2, DS, di)};
             R pid[9], ql[4];
 #pragma unroll
-            for (int c = 0; c < 9; ++c) pid[c] = ld(p.drone, 13 + c, DS, di);
+            for (int c = 0; c < 9; ++c) pid[c] = ld(p.drone, kRowPid + c, DS, di);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ql[c] = ld(p.drone, 22 + c, DS, di);   // Bullet's cached link frame
+            for (int c = 0; c < 4; ++c) ql[c] = ld(p.drone, kRowLink + c, DS, di);   // Bullet's cached link frame
             float a[4];
             if (p.flags & CH_STEP_RANDOM_ACTIONS) {
                 uint32_t c4[4] = {(uint32_t)stepi, 0u, (uint32_t)t, (uint32_t)(p.env_off + e)};
@@ -239,19 +240,20 @@ __global__ __launch_bounds__(64) void k_env(StepParams<R> p) {
             }
             R* D = p.drone;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) D[(22 + c) * DS + di] = ql[c];
+            for (int c = 0; c < 4; ++c) D[(kRowLink + c) * DS + di] = ql[c];
             if (p.evald) p.evald[di] = eval_distance_step(p.evald[di], sc == 0, px0, py0, pos[0], pos[1]);
-            D[0 * DS + di] = pos[0]; D[1 * DS + di] = pos[1]; D[2 * DS + di] = pos[2];
+            D[kRowPos * DS + di] = pos[0]; D[(kRowPos + 1) * DS + di] = pos[1]; D[(kRowPos + 2) * DS + di] = pos[2];
             if constexpr (MIX) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) p.pos64[c * DS + di] = pd[c];
                 S.dxd[t] = pd[0]; S.dyd[t] = pd[1];
             }
-            D[3 * DS + di] = q[0]; D[4 * DS + di] = q[1]; D[5 * DS + di] = q[2]; D[6 * DS + di] = q[3];
-            D[7 * DS + di] = v[0]; D[8 * DS + di] = v[1]; D[9 * DS + di] = v[2];
-            D[10 * DS + di] = w[0]; D[11 * DS + di] = w[1]; D[12 * DS + di] = w[2];
+            D[kRowQuat * DS + di] = q[0]; D[(kRowQuat + 1) * DS + di] = q[1]; D[(kRowQuat + 2) * DS + di] = q[2];
+            D[(kRowQuat + 3) * DS + di] = q[3];
+            D[kRowVel * DS + di] = v[0]; D[(kRowVel + 1) * DS + di] = v[1]; D[(kRowVel + 2) * DS + di] = v[2];
+            D[kRowOmega * DS + di] = w[0]; D[(kRowOmega + 1) * DS + di] = w[1]; D[(kRowOmega + 2) * DS + di] = w[2];
 #pragma unroll
-            for (int c = 0; c < 9; ++c) D[(13 + c) * DS + di] = pid[c];
+            for (int c = 0; c < 9; ++c) D[(kRowPid + c) * DS + di] = pid[c];
             quat_to_euler(q, rpy);
             S.dx[t] = pos[0]; S.dy[t] = pos[1];
             own_z = pos[2];

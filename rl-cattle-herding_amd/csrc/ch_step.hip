@@ -1,5 +1,6 @@
 // ch_step.hip — the kernels and launchers of the fused env-step, v2: k_step2 and k_step2_actor around step2_body
-// (ch_step_body.h, which holds the design comment), the geometry dispatch, and the explicit instantiations.
+// (ch_step_body.h, which holds the design comment; ch_step_sync.h the hand-off primitives, ch_step_flock.h the flock
+// math), the geometry dispatch, and the explicit instantiations.
 #include "ch_step_body.h"
 #include "ch_mlp2_dev.h"   // mlp2_body (k_step2_actor)
 

@@ -22,6 +22,8 @@
 // The hand-offs are LDS counters (release/acquire at workgroup scope, LDS only); the two workgroup
 // barriers are LDS-only too, so no wave ever waits for its own global stores to drain.  Auto-resets
 // (rare) run after the second barrier.  The SoA state layout is shared with ch_kernels.hip.
+// The barriers, hand-off counters, stamp macros and the pipelined step loop's protocol (V2Pipe) are in ch_step_sync.h, the
+// cow waves' flock math in ch_step_flock.h; this file keeps the LDS carve, the observation writers and the step itself.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +32,7 @@
 #include "ch_common.h"
 #include "ch_device.h"
 #include "ch_internal.h"
+#include "ch_step_sync.h"
 
 namespace ch {
 
@@ -68,18 +71,6 @@ __device__ __forceinline__ int qdiv(int q, int d, float rd) {
     return r;
 }
 
-// workgroup barrier that orders LDS only (no wait for outstanding global stores)
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-// LDS writes of this wave visible to its other lanes
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 // Quad broadcast: lane K of every group of four lanes, to all four (DPP quad_perm: a VALU move, no LDS traffic).
 // Called convergently by the whole wave.  With four drones per env the drones of an env are one quad of the drone wave.
 template <int K> __device__ __forceinline__ int qb(int x) {
@@ -95,85 +86,6 @@ template <int K> __device__ __forceinline__ double qb(double x) {
 template <class T> __device__ __forceinline__ void qall(T x, T out[4]) {
     out[0] = qb<0>(x); out[1] = qb<1>(x); out[2] = qb<2>(x); out[3] = qb<3>(x);
 }
-
-// called convergently by a whole wave: its LDS writes are published, then the counter is bumped once
-__device__ __forceinline__ void lds_signal(int* f) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ int lds_peek(int* f) {
-    return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// a hand-off that never completed: the kernel goes on (never a hang) and the handle's device error
-// word records it; ch_metrics / ch_get_state / ch_sync return CH_ERR_DEVICE from then on
-__device__ __forceinline__ void handoff_failed(int* err) {
-    if (err && (threadIdx.x & 63) == 0) atomicOr(err, CH_DEVERR_HANDOFF);
-}
-// diagnostics (-DCH_COUNT_SPINS builds only, tools/spin_split.py): sleep iterations of the hand-off waits, per wave
-// kind (drone wave, cow waves), and the number of waits, summed over every k_step2 launch since the last read
-#ifdef CH_COUNT_SPINS
-static __device__ unsigned long long g_ch_spins[4];
-__device__ __forceinline__ void spin_note(int n) {
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x < 64 ? 0 : 1;
-        atomicAdd(&g_ch_spins[w], (unsigned long long)n);
-        atomicAdd(&g_ch_spins[2 + w], 1ull);
-    }
-}
-#else
-__device__ __forceinline__ void spin_note(int) {}
-#endif
-// spin until *f >= target (bounded, about 0.1 s)
-__device__ __forceinline__ void lds_wait(int* f, int target, int* err) {
-    int spins = 0;
-    while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target && ++spins < (1 << 22))
-        __builtin_amdgcn_s_sleep(1);
-    if (spins >= (1 << 22)) handoff_failed(err);
-    spin_note(spins);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// Dynamic share-out of a cow-wave loop: each call hands the calling wave the next n items of the
-// counter.  The cow waves do not run at equal speed (one of them shares its SIMD with the other
-// resident workgroup's prioritised drone wave), so a static lane -> item split leaves the slowest
-// wave with as many items as the fastest.
-__device__ __forceinline__ int grab(int* ctr, int n, bool skip = false) {
-    if (skip) return 1 << 28;   // (wave-uniform) this wave takes no more items of the loop
-    int b = 0;
-    if ((threadIdx.x & 63) == 0) b = atomicAdd(ctr, n);
-    return __builtin_amdgcn_readfirstlane(b);
-}
-
-// barrier among the cow waves only (the drone wave keeps running); `global` also publishes their
-// global stores (needed before other cow lanes rewrite the same state)
-__device__ __forceinline__ void cow_sync(int* f, int waves, bool global, int* err) {
-    if (global) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    lds_signal(f);
-    lds_wait(f, waves, err);
-    if (global) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// diagnostics: per-workgroup timestamps (slots: 0/1 wall clock at start/end, 2 shader clock at start,
-// 3 after the first barrier, 4 drone chain done, 5 reward terms done, 6 herded flags received,
-// 7 bookkeeping done, 8 cow waves: alpha rows done, 9 drone positions received, 10 velocity update
-// done, 11 obs copy done, 12 CU id, 13 second barrier, 14 end)
-#define TS(slot, val) do { if (!PIPE && p.tstamp) p.tstamp[(long long)blockIdx.x * 128 + (slot)] = (val); } while (0)
-// diagnostics: per cow wave 1..6, chunks taken and cycles spent in each dynamic loop (slots 64 + 10 (w - 1) + 2 loop)
-#define CHUNK_T0 const long long ck0_ = (!PIPE && p.tstamp) ? (long long)clock64() : 0
-// diagnostics: the latest of the cow waves at a point (per-workgroup max of the shader clock in slot `slot`)
-#define TS_MAX(slot) do { if (!PIPE && p.tstamp && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.tstamp + (long long)blockIdx.x * 128 + (slot)), (unsigned long long)clock64()); } while (0)
-#define CHUNK_T1(loop) do { if (!PIPE && p.tstamp && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) <= 6) { long long* q_ = p.tstamp + (long long)blockIdx.x * 128 + 64 + 10 * ((threadIdx.x >> 6) - 1) + 2 * (loop); q_[0] += 1; q_[1] += (long long)clock64() - ck0_; } } while (0)
-
-// (step2_body's PIPE instantiations write none of the slots above: its waves are in different steps at once.)  The
-// pipelined step loop's own stamps, 16 slots per step for the first 8 steps of a launch (slot 16 k + i), shader clock:
-//   drone wave of step k: 0 at the P_N wait (step 0: launch start), 1 chain start, 2 D published, 3 H received,
-//   4 R published, 5 P_N signalled, 6 env scalars written back (P_B), 7 books closed (P_K), with the wave's SIMD in
-//   bits 62-63
-//   cow waves: 8 first cow wave enters step k (at the P_B wait), 9 past P_B and P_C, 10 waits for D, 11 D seen,
-//   12 flock work done, waits for R (first cow wave), 13 the same, latest cow wave, 14 R seen (first cow wave),
-//   15 step end, latest cow wave
-#define PTS(i, val) do { if (PIPE && p.tstamp && kstep < 8) p.tstamp[(long long)blockIdx.x * 128 + 16 * kstep + (i)] = (val); } while (0)
-#define PTS_MAX(i) do { if (PIPE && p.tstamp && kstep < 8 && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.tstamp + (long long)blockIdx.x * 128 + 16 * kstep + (i)), (unsigned long long)clock64()); } while (0)
 
 template <class R>
 struct V2Smem {
@@ -374,442 +286,11 @@ __device__ __forceinline__ R cattle_term(const V2Smem<R>& S, int u, int M, R cc)
     return cattle_spacing(sqrt(best), cc);
 }
 
-// flock alpha term, pair form, for every flocking env (flockUtils.py:237-258, 327-337; MathUtils 11-58):
-// one table of the workgroup's unordered cow pairs, evaluated in the bump's support only.  The bump is
-// exactly 0 for sigma_norm(|z|) / r_alpha > 1 (beyond the lattice range d_alpha = 1.2 m); such a pair adds
-// +-0 to both rows, which leaves a row sum that starts at +0 unchanged.  A cheap pass over every pair (no
-// square root) marks the pairs with |z|^2 <= 1.44 (1 + 1e-9) -- a superset of the support, see
-// kAlphaSupport2 -- in both cows' neighbour masks and appends them to a queue; the full evaluation runs on
-// full waves of queued pairs; the rows visit the masked neighbours in ascending order like the dense loop.
-constexpr double kAlphaSupport2 = 1.44 * (1.0 + 1e-9);
+}  // namespace ch
 
-// |z| <= 999 (the sensing range) from |z|^2 without the square root away from the boundary: sqrt is
-// correctly rounded and monotonic, and sqrt(998001) = 999 exactly
-template <class R> __device__ __forceinline__ bool in_sensing(R n2) {
-    bool s = n2 <= R(998001.0);
-    if (!s && n2 < R(998010.0)) s = sqrt(n2) <= R(999);
-    return s;
-}
+#include "ch_step_flock.h"
 
-// Cow j of env g has another cow of its env within sensing range (flockUtils.py:237-258: the alpha sums run over the
-// neighbours inside r = 999 m; with none, its alpha term is 0).  One partner decides it almost always -- the next cow --
-// and only a cow out of that one's range scans the rest, with the pair's difference taken in the pair list's order
-// (the same n2 as the cheap pass).  Evaluated by the row instead of marked by the cheap pass: those byte stores (many
-// lanes of a pass chunk on the same cow) took ~40 % of the pass (tools/wg_trace.py, profiles/r04/zc).
-template <class R>
-__device__ __forceinline__ bool has_sensing_neighbour(const V2Smem<R>& S, int M, int g, int j) {
-    auto ins = [&](int k) {
-        const int lo = g * M + min(j, k), hi = g * M + max(j, k);
-        const R zx = S.cx[hi] - S.cx[lo], zy = S.cy[hi] - S.cy[lo];
-        return in_sensing(zx * zx + zy * zy);
-    };
-    bool has = M > 1 && ins(j + 1 < M ? j + 1 : 0);
-    if (!has)
-        for (int k = 0; k < M; ++k)
-            if (k != j && ins(k)) { has = true; break; }
-    return has;
-}
-
-template <class R>
-__device__ __forceinline__ void alpha_cheap(V2Smem<R>& S, int* fl, int M, int P, int nf, const int* flist, bool skip) {
-    const float rP = 1.0f / (float)P;
-    const int lane = threadIdx.x & 63;
-    for (;;) {
-        const int b = grab(fl + C_PAIRS, 64, skip);
-        if (b >= nf * P) break;
-        const int q = b + lane;
-        bool cand = false;
-        int gi = 0;
-        if (q < nf * P) {
-            const int f = qdiv(q, P, rP), r = q - f * P, g = flist[f];
-            const uint32_t pr = S.pl[r];
-            const int li = pr & 0xff, hi = pr >> 8;
-            const int bi = g * M + li, bj = g * M + hi;
-            const R zx = S.cx[bj] - S.cx[bi], zy = S.cy[bj] - S.cy[bi];
-            const R n2 = zx * zx + zy * zy;
-            cand = n2 <= R(kAlphaSupport2);
-            if (cand) {
-                atomicOr(&S.nbm[bi], 1ull << hi);
-                atomicOr(&S.nbm[bj], 1ull << li);
-            }
-            gi = g * P + r;
-        }
-        const unsigned long long m = __ballot(cand);
-        int base = 0;
-        if (lane == 0 && m) base = atomicAdd(fl + Q_LEN, (int)__popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (cand) S.queue[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)gi;
-    }
-}
-
-// The full evaluation of the queued pairs, streamed (the barrier form is in DESIGN_HISTORY.md): a wave
-// that runs out of cheap-pass chunks starts on the queue at once instead of waiting at a pass-wide barrier for
-// the other waves' last cheap chunks.  Every queue slot starts as kQEmpty (phase 0); a chunk of 64 slots is taken
-// when all of them are reserved (Q_LEN) or the cheap pass is complete (F_C counts the waves done with it, so
-// Q_LEN is then final), and each lane waits for its own slot's pair index to be written -- a per-slot ready mark.
-constexpr uint16_t kQEmpty = 0xFFFF;
-template <class R>
-__device__ __forceinline__ void alpha_full(V2Smem<R>& S, int* fl, int M, int P, bool skip, int W1, int* err) {
-    const R ra = sigma_norm_n(R(1.2)), da = ra;
-    const float rP = 1.0f / (float)P;
-    const int lane = threadIdx.x & 63;
-    for (;;) {
-        const int b = grab(fl + C_QUEUE, 64, skip);
-        if (b >= (1 << 28)) break;   // (skip)
-        int qn = 0;
-        bool done = false;
-        int spins = 0;
-        for (;; ++spins) {
-            done = lds_peek(fl + F_C) >= W1;      // F_C before Q_LEN: once every wave is done, Q_LEN is final
-            qn = lds_peek(fl + Q_LEN);
-            if (done || qn >= b + 64) break;
-            if (spins >= (1 << 22)) { handoff_failed(err); done = true; break; }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        spin_note(spins);
-        if (b >= qn) break;   // done: no slot of this chunk was ever reserved
-        if (b + lane < qn) {
-            int gi = kQEmpty;
-            for (int spins = 0; spins < (1 << 22); ++spins) {
-                gi = *reinterpret_cast<volatile const uint16_t*>(&S.queue[b + lane]);
-                if (gi != kQEmpty) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (gi == kQEmpty) { handoff_failed(err); gi = 0; }
-            const int g = qdiv(gi, P, rP), r = gi - g * P;
-            const uint32_t pr = S.pl[r];
-            const int bi = g * M + (pr & 0xff), bj = g * M + (pr >> 8);
-            const R zx = S.cx[bj] - S.cx[bi], zy = S.cy[bj] - S.cy[bi];
-            const R nrm = sqrt(zx * zx + zy * zy);
-            R gx = 0, gy = 0, cx = 0, cy = 0;
-            pair_terms_n(nrm, zx, zy, S.cvx[bi], S.cvy[bi], S.cvx[bj], S.cvy[bj], ra, da, gx, gy, cx, cy);
-            S.tgx[gi] = gx; S.tgy[gi] = gy; S.tcx[gi] = cx; S.tcy[gi] = cy;
-        }
-    }
-}
-
-// alpha row of cow u = g*M + j in neighbour order over its masked neighbours, scaled by c2_alpha
-// (flockUtils.py:237-258); the two directed contributions of a pair are exact negations
-template <class R>
-__device__ __forceinline__ void alpha_row(V2Smem<R>& S, int M, int P, int u, int g, int j) {
-    const R C2A = R(2 * 1.7320508075688772);
-    R gx = 0, gy = 0, cxx = 0, cyy = 0, ux = 0, uy = 0;
-    const int pb = g * P;
-    // Four neighbours per round, branch-free: the table loads of a round are issued together (an empty slot
-    // reads the env's first pair), then summed in neighbour order.  An empty slot adds +0, which leaves the
-    // sum unchanged: it starts at +0 and a round-to-nearest sum is -0 only if both addends are.
-    for (unsigned long long m = S.nbm[u]; m;) {
-        R t[4][4];
-        bool v[4], fwd[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            v[r] = m != 0;
-            const int k = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            fwd[r] = j < k;
-            const int idx = v[r] ? pb + tri(min(j, k), max(j, k), M) : pb;
-            t[r][0] = S.tgx[idx]; t[r][1] = S.tgy[idx]; t[r][2] = S.tcx[idx]; t[r][3] = S.tcy[idx];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            gx += v[r] ? (fwd[r] ? t[r][0] : -t[r][0]) : R(0); gy += v[r] ? (fwd[r] ? t[r][1] : -t[r][1]) : R(0);
-            cxx += v[r] ? (fwd[r] ? t[r][2] : -t[r][2]) : R(0); cyy += v[r] ? (fwd[r] ? t[r][3] : -t[r][3]) : R(0);
-        }
-    }
-    if (has_sensing_neighbour(S, M, g, j)) { ux = C2A * gx + C2A * cxx; uy = C2A * gy + C2A * cyy; }
-    S.aux[u] = ux; S.auy[u] = uy;
-}
-
-// ---- per-wave env tables (V2Layout W > 0, large herds) ---------------------------------------------
-// Env g's alpha pair table in the calling wave's slot: gradient x, y and the bump b per pair
-// (flockUtils.py:237-258, 327-337).  The consensus term b (p_hi - p_lo) is not stored: alpha_row_pw
-// recomputes it from the velocities with the same rounding.
-//
-// Sparse in the bump's support.  The bump is exactly 0 for sigma_norm(|z|) / r_alpha > 1, i.e. beyond
-// the lattice range d_alpha = 1.2 m, and such a pair adds +-0 to both rows, which leaves a row sum that
-// starts at +0 unchanged.  A cheap pass over all pairs (no square root) queues the pairs with
-// |z|^2 <= 1.44 (1 + 1e-9) -- a superset of the support: any pair beyond it has z > 1 + 5e-10 exactly and
-// z > 1 as computed -- and marks them in both cows' neighbour masks; the full evaluation (square roots,
-// the bump's cos, sigma_1, divisions) runs on full waves of queued pairs only, and the rows visit only
-// masked neighbours, in ascending neighbour order like the dense loop.
-template <class R>
-__device__ __forceinline__ void alpha_cheap_pw(V2Smem<R>& S, int M, int P, int g, uint16_t* qu, int& qn) {
-    const int lane = threadIdx.x & 63;
-    for (int r0 = 0; r0 < P; r0 += 64) {
-        const int r = r0 + lane;
-        bool cand = false;
-        if (r < P) {
-            const uint32_t pr = S.pl[r];
-            const int li = pr & 0xff, hi = pr >> 8;
-            const int bi = g * M + li, bj = g * M + hi;
-            const R zx = S.cx[bj] - S.cx[bi], zy = S.cy[bj] - S.cy[bi];
-            const R n2 = zx * zx + zy * zy;
-            cand = n2 <= R(kAlphaSupport2);
-            if (cand) {
-                atomicOr(&S.nbm[bi], 1ull << hi);
-                atomicOr(&S.nbm[bj], 1ull << li);
-            }
-        }
-        const unsigned long long m = __ballot(cand);
-        if (cand) qu[qn + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)r;
-        qn += __popcll(m);
-    }
-}
-
-// The same pass for a geometry-specialised herd (NC = the pass's 64-pair chunks, a compile-time count): the lane's
-// pair words come from registers (prw, read from LDS once per kernel) and every chunk's position loads are issued
-// before any chunk's test, so the pass costs about one LDS round trip instead of one per chunk.  The queue and
-// masks are filled in the same (chunk, lane) order as alpha_cheap_pw.
-template <class R, int NC>
-__device__ __forceinline__ void alpha_cheap_pw_b(V2Smem<R>& S, int M, int P, int g, uint16_t* qu, int& qn,
-                                                 const uint32_t (&prw)[NC]) {
-    const int lane = threadIdx.x & 63;
-    R n2[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const uint32_t pr = prw[c];
-        const int bi = g * M + (pr & 0xff), bj = g * M + (pr >> 8);
-        const R zx = S.cx[bj] - S.cx[bi], zy = S.cy[bj] - S.cy[bi];
-        n2[c] = zx * zx + zy * zy;
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int r = 64 * c + lane;
-        bool cand = false;
-        if (r < P) {
-            const uint32_t pr = prw[c];
-            const int li = pr & 0xff, hi = pr >> 8;
-            const int bi = g * M + li, bj = g * M + hi;
-            cand = n2[c] <= R(kAlphaSupport2);
-            if (cand) {
-                atomicOr(&S.nbm[bi], 1ull << hi);
-                atomicOr(&S.nbm[bj], 1ull << li);
-            }
-        }
-        const unsigned long long m = __ballot(cand);
-        if (cand) qu[qn + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)r;
-        qn += __popcll(m);
-    }
-}
-
-template <class R>
-__device__ __forceinline__ void alpha_full_pw(V2Smem<R>& S, int M, int P, int g, int q0, int qn, R* tb,
-                                              const uint16_t* qu) {
-    const R ra = sigma_norm_n(R(1.2)), da = ra;
-    const int q = q0 + (threadIdx.x & 63);
-    if (q >= qn) return;
-    const int r = qu[q];
-    const uint32_t pr = S.pl[r];
-    const int bi = g * M + (pr & 0xff), bj = g * M + (pr >> 8);
-    const R zx = S.cx[bj] - S.cx[bi], zy = S.cy[bj] - S.cy[bi];
-    const R nrm = sqrt(zx * zx + zy * zy);
-    R gx = 0, gy = 0, cx = 0, cy = 0;
-    const R b = pair_terms_n(nrm, zx, zy, R(0), R(0), R(0), R(0), ra, da, gx, gy, cx, cy);
-    tb[r] = gx; tb[P + r] = gy; tb[2 * P + r] = b;
-}
-
-// alpha row of cow j of env g from the wave's slot, in neighbour order (as alpha_row), visiting the
-// masked neighbours only.  The pair's consensus term is b * (p_hi - p_lo), hi/lo the pair's cows,
-// exactly as the shared table holds it.
-template <class R>
-__device__ __forceinline__ void alpha_row_pw(V2Smem<R>& S, int M, int P, int g, int j, const R* tb) {
-    const R C2A = R(2 * 1.7320508075688772);
-    const int u = g * M + j;
-    R gx = 0, gy = 0, cxx = 0, cyy = 0, ux = 0, uy = 0;
-    const R pjx = S.cvx[u], pjy = S.cvy[u];
-    // four neighbours per round, branch-free as in alpha_row (an empty slot reads pair 0 / cow j, adds +0)
-    for (unsigned long long m = S.nbm[u]; m;) {
-        R t[4][5];
-        bool v[4], fwd[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            v[r] = m != 0;
-            const int k = v[r] ? __ffsll((long long)m) - 1 : j;
-            m &= m - 1;
-            fwd[r] = j < k;
-            const int idx = v[r] ? tri(min(j, k), max(j, k), M) : 0;
-            t[r][0] = tb[idx]; t[r][1] = tb[P + idx]; t[r][2] = tb[2 * P + idx];
-            t[r][3] = S.cvx[g * M + k]; t[r][4] = S.cvy[g * M + k];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const R b = t[r][2], pkx = t[r][3], pky = t[r][4];
-            const R dvx = fwd[r] ? pkx - pjx : pjx - pkx, dvy = fwd[r] ? pky - pjy : pjy - pky;
-            const R tcx = b * dvx, tcy = b * dvy;
-            gx += v[r] ? (fwd[r] ? t[r][0] : -t[r][0]) : R(0); gy += v[r] ? (fwd[r] ? t[r][1] : -t[r][1]) : R(0);
-            cxx += v[r] ? (fwd[r] ? tcx : -tcx) : R(0); cyy += v[r] ? (fwd[r] ? tcy : -tcy) : R(0);
-        }
-    }
-    if (has_sensing_neighbour(S, M, g, j)) { ux = C2A * gx + C2A * cxx; uy = C2A * gy + C2A * cyy; }
-    S.aux[u] = ux; S.auy[u] = uy;
-}
-
-// the shepherd term of a drone closer than 1 m (mu < 1: the projected agent q_ik lies between cow and drone),
-// the general pair_terms evaluation.  Rare, so it is kept out of line: inlined at each of the unrolled drone
-// slots of shepherd_sum it would add ~1.2k instructions to the kernel's instruction-cache footprint.
-template <class R> struct Terms4 { R gx, gy, cx, cy; };
-template <class R>
-__device__ __noinline__ Terms4<R> near_drone_terms(R qix, R qiy, R pix, R piy, R yx, R yy, R mu, R pkx, R pky) {
-    const R ra_b = sigma_norm_n(R(1.0)), da_b = ra_b;
-    R qkx = mu * qix + (R(1) - mu) * yx, qky = mu * qiy + (R(1) - mu) * yy;
-    Terms4<R> t = {0, 0, 0, 0};
-    pair_terms(qix, qiy, pix, piy, qkx, qky, pkx, pky, ra_b, da_b, t.gx, t.gy, t.cx, t.cy);
-    return t;
-}
-
-// shepherd (delta, flockUtils.py:271-317) and predator (343-348) terms of drone k on cow u = g*M + j:
-// t[0..3] the delta gradient and consensus parts, t[4..5] the predator push; returns in-range | predator << 1
-template <class R>
-__device__ __forceinline__ int delta_vals(const V2Smem<R>& S, int N, int u, int g, int k, R t[6]) {
-    const R qix = S.cx[u], qiy = S.cy[u], pix = S.cvx[u], piy = S.cvy[u];
-    const R yx = S.dx[g * N + k], yy = S.dy[g * N + k];
-    const R ex = yx - qix, ey = yy - qiy;
-    const R dn = sqrt(ex * ex + ey * ey);   // = the distance table entry
-    const bool in = dn <= R(999 + 2), pr = dn <= R(1.1);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) t[c] = 0;
-    if (in) {
-        R difx = qix - yx, dify = qiy - yy;
-        R d = dn + R(1e-6);
-        R mu = d / R(1.0) < R(1.0) ? d / R(1.0) : R(1.0);
-        R akx = difx / d, aky = dify / d;
-        R P00 = R(1) - akx * akx, P01 = R(0) - akx * aky, P10 = R(0) - aky * akx, P11 = R(1) - aky * aky;
-        R pkx = mu * (P00 * pix + P01 * piy), pky = mu * (P10 * pix + P11 * piy);
-        if (mu == R(1) && isfinite(yx) && isfinite(yy) && isfinite(qix) && isfinite(qiy)) {
-            // a drone 1 m away or more: q_ik = 1 q_i + 0 y_k = q_i exactly, so pair_terms sees z = +0:
-            // |z| = 0, den = 1, sigma_norm = 0, bump(0) = 1, gradient ph * (0 / 1) = +-0 (+0 in the table),
-            // consensus 1 * (p_ik - p_i) -- the same values without the square roots and divisions
-            t[2] = pkx - pix;
-            t[3] = pky - piy;
-        } else {
-            const Terms4<R> n4 = near_drone_terms(qix, qiy, pix, piy, yx, yy, mu, pkx, pky);
-            t[0] = n4.gx; t[1] = n4.gy; t[2] = n4.cx; t[3] = n4.cy;
-        }
-    }
-    if (pr) {
-        R d3 = cube(dn);
-        t[4] = R(-650000.0) * ex / d3;
-        t[5] = R(-650000.0) * ey / d3;
-    }
-    return (int)in | ((int)pr << 1);
-}
-
-// the same terms, one (cow, drone) item per lane, stored in the term table for flock_combine
-template <class R>
-__device__ __forceinline__ void delta_term(V2Smem<R>& S, int N, int u, int g, int k, R* td, uint8_t* tdf, int i,
-                                           int T) {
-    R t[6];
-    const int f = delta_vals(S, N, u, g, k, t);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) td[c * T + i] = t[c];
-    tdf[i] = (uint8_t)f;
-}
-
-// the shepherd/predator sum of cow u over its env's n live drones in drone order (flockUtils.py:271-348),
-// one cow per lane with the drone terms in registers: delta = c2_beta (sum grad + sum consensus) over the
-// drones in range, plus the predator pushes.  A term out of range is +0, which leaves a sum that starts at
-// +0 unchanged (the same sums flock_combine forms from the term table).
-template <class R, int NT>
-__device__ __forceinline__ void shepherd_sum(const V2Smem<R>& S, int N, int u, int g, int n, R& ddx, R& ddy) {
-    const R C2B = R(2 * 4.47213595499958);
-    R gx = 0, gy = 0, cxx = 0, cyy = 0, sx = 0, sy = 0;
-    int nb = 0;
-    constexpr int NK = NT ? NT : 64;
-    CH_UNROLL for (int k = 0; k < NK; ++k) {
-        if (k >= N || k >= n) break;
-        R t[6];
-        const int f = delta_vals(S, N, u, g, k, t);
-        if (f & 1) { ++nb; gx += t[0]; gy += t[1]; cxx += t[2]; cyy += t[3]; }
-        if (f & 2) { sx += t[4]; sy += t[5]; }
-    }
-    ddx = 0; ddy = 0;
-    if (nb > 0) { ddx = C2B * gx + C2B * cxx; ddy = C2B * gy + C2B * cyy; }
-    ddx += sx; ddy += sy;
-}
-
-// gamma term (flockUtils.py:150-160, 340-341) and the velocity update with the speed clip
-// (BaseAviary.py:1384-1400) of cow u from its alpha row (aux, auy) and shepherd sum (ddx, ddy)
-// nv != nullptr: the new velocity goes to LDS (nv[u], nv[GM + u]) instead of HBM
-template <class R>
-__device__ __forceinline__ void velocity_update(const StepParams<R>& p, const V2Smem<R>& S, int M, int e0, int u, R ddx,
-                                                R ddy, R* nv = nullptr, int GM = 0) {
-    const long long CS = (long long)p.E * M;
-    const R C1G = R(5), C2G = R(0.2 * 2.23606797749979);
-    const R qix = S.cx[u], qiy = S.cy[u], pix = S.cvx[u], piy = S.cvy[u];
-    R gmx = -C1G * sigma_1(qix - R(1)) - C2G * pix, gmy = -C1G * sigma_1(qiy - R(1)) - C2G * piy;
-    R qx = (S.aux[u] + ddx) + gmx, qy = (S.auy[u] + ddy) + gmy;
-    const R dt_sqr = R(0.05 * 0.05);
-    R vx = pix + qx * dt_sqr, vy = piy + qy * dt_sqr;
-    R sp = norm2(vx, vy);
-    if (sp > R(kMaxVelCattle)) { R f = R(kMaxVelCattle) / sp; vx *= f; vy *= f; }
-    if (nv) { nv[u] = vx; nv[GM + u] = vy; return; }
-    const long long ci = (long long)e0 * M + u;
-    CH_STS(&p.cattle[2 * CS + ci], vx); CH_STS(&p.cattle[3 * CS + ci], vy);
-}
-
-// the drone terms of cow u from the term table summed in drone order, then the velocity update.  A term
-// out of range is +0 in the table, and adding +0 to a sum that starts at +0 leaves it unchanged, so only
-// the count needs the flag.
-template <class R>
-__device__ __forceinline__ void flock_combine(const StepParams<R>& p, V2Smem<R>& S, int N, int M, int e0, int u, int n,
-                                              const R* td, const uint8_t* tdf, int ib, int T) {
-    const R C2B = R(2 * 4.47213595499958);
-    R ddx = 0, ddy = 0, sx = 0, sy = 0, gx = 0, gy = 0, cxx = 0, cyy = 0;
-    int nb = 0;
-    CH_UNROLL for (int k = 0; k < N; ++k) {
-        if (k >= n) break;
-        const int i = ib + k;
-        const int f = tdf[i];
-        if (f & 1) { ++nb; gx += td[i]; gy += td[T + i]; cxx += td[2 * T + i]; cyy += td[3 * T + i]; }
-        if (f & 2) { sx += td[4 * T + i]; sy += td[5 * T + i]; }
-    }
-    if (nb > 0) { ddx = C2B * gx + C2B * cxx; ddy = C2B * gy + C2B * cyy; }
-    ddx += sx; ddy += sy;
-    velocity_update(p, S, M, e0, u, ddx, ddy);
-}
-
-// LDS of the pipelined step loop (k_step2_multi, configs[3] f64), placed after the V2Layout carve:
-//   ho   [27][64]  per drone lane: the 26 state reals after the chain (a reset env: its new body) and evald's accumulator
-//   hoi  [2][64]   NUM_DRONES of the lane's env for the next step, the Philox step counter
-//   d1   [7][64]   the odd steps' copy of S.dx, dy, dz, dq (the even steps use the V2Layout arrays)
-//   met  [kMetricRows][16]  the metric rows of the workgroup's envs, owned by the books waves for the length of the
-//                  launch: staged from global memory by the cow waves in step 0 only (before F_E of step 0), then read,
-//                  updated and written back by the books wave of every step (which also stores them to global memory
-//                  every step).  The cow waves never touch them after step 0.
-//   flags1 [kV2Flags]  the odd steps' hand-off and work counters (the even steps: S.flags)
-//   sync           counters that run over the whole launch, never cleared inside it:
-//       P_N  = steps whose hand-off is final       (drone wave k -> drone wave k+1; target k+1)
-//       P_B  = steps whose env scalars are written back (drone wave k -> cow waves; target k+1).  It guards the global
-//              rows envi / envr / stale / obs_tag, which the cow waves load on entering step k+1, and the LDS rows they
-//              restage there (S.ei, S.prev, S.clock and the cow and pair tables): the books wave of step k reads none
-//              of them after this signal.  It does not say that the books are closed.
-//       P_C  = cow waves done with a step, summed  (cow waves among themselves; target W1 (k+1))
-//       P_K  = steps whose books are closed        (drone wave k -> cow waves and drone wave k+1; target k+1): the
-//              reward, term / trunc, metrics and episode records of step k are stored (released at workgroup scope) and
-//              that wave is done with S.dcow (the closest-cow search) and X.met.  The cow waves wait for it before the
-//              per-cow pass of step k+1, the first thing that overwrites S.dcow; the books wave of step k+1 waits for
-//              it before it touches X.met or stores to the rows above.
-//       P_SIMD + w = 1 + the SIMD of drone wave w
-// Invariant: step k uses counter set k & 1; that set is zero when step k's first signal can arrive (step 0 and 1: cleared
-// before the launch's only barrier; step k >= 2: cleared by the cow waves on entering step k-1, see phase 0).
-// S.LT and S.pl (the curriculum table and the pair list) are constant: staged once per launch (step2_pipe_init), so the
-// books wave may read LT whatever step the cow waves are in.
-template <class R>
-struct V2Pipe {
-    enum { P_N = 0, P_B, P_C, P_SIMD, P_K = P_SIMD + 2, P_COUNT = 8 };
-    static_assert(P_K < P_COUNT, "launch-long counters");
-    static constexpr int kMetG = 16;   // envs per workgroup of the pipelined instantiation
-    static constexpr size_t kBytes = (27 + 7) * 64 * sizeof(R) + (size_t)kMetricRows * kMetG * sizeof(double) +
-                                     (2 * 64 + kV2Flags + P_COUNT) * sizeof(int);
-    R *ho, *d1;
-    double* met;
-    int *hoi, *flags1, *sync;
-    __device__ explicit V2Pipe(unsigned char* base) {
-        ho = (R*)base; d1 = ho + 27 * 64;
-        met = (double*)(d1 + 7 * 64);
-        hoi = (int*)(met + kMetricRows * kMetG); flags1 = hoi + 2 * 64; sync = flags1 + kV2Flags;
-    }
-};
+namespace ch {
 
 // ---- env scalars back to HBM from the env lanes' registers (nothing after this step reads them).  A macro, expanded
 // at one of two places in step2_body: at its end, or (PIPE) ahead of the reward; it reads step2_body's locals (the f_*
@@ -877,14 +358,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
     const V2Pipe<R> X(smem + (PIPE ? L.bytes() : 0));
     int* const ps = X.sync;
     int* const flags0 = S.flags;   // the even steps' counter set
-    if constexpr (PIPE) {
-        // the step's copy of the arrays the cow waves read from the drone wave, and its set of hand-off counters
-        if (kstep & 1) {
-            S.dx = X.d1; S.dy = S.dx + G * N; S.dz = S.dy + G * N; S.dq = S.dz + G * N;
-            S.dxd = (double*)S.dx; S.dyd = (double*)S.dy;
-            S.flags = X.flags1;
-        }
-    }
+    if constexpr (PIPE) X.select_step(S, kstep, G * N);
     const int e0 = (blockIdx.x + salt) * G;
     const int Gv = min(G, p.E - e0);
     const long long E = p.E, DS = E * N, CS = E * M;
@@ -929,24 +403,13 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
         if (ROLE == 2 && ct == 0) PTS(8, (long long)clock64());
         if (kstep > 0) {
             if (ROLE == 2) {
-                // (a) step k's loads come after step k-1's stores: the books wave's write-back of the env scalars
-                // (envi, envr, stale, obs_tag: P_B, released at workgroup scope by that wave, which reads none of the
-                // LDS rows restaged below after it) and every cow wave's final pass (P_C, a cow-wave barrier that
-                // publishes their global stores).  The books of step k-1 may still be open here: their wave reads
-                // only its registers, the constant S.LT, X.met (never touched by the cow waves after step 0) and
-                // S.dcow, which this step overwrites only behind the P_K wait ahead of the per-cow pass.  (c) the
-                // outputs of step k are ordered after those of step k-1 through P_K: that wait precedes this step's
-                // cow items (F_H), which the books of step k wait for, and the books wave of step k waits for P_K
-                // itself before its output stores.
+                // V2Pipe's ordering (a): behind P_B and the cow-wave barrier P_C, which publishes their global stores
                 lds_wait(ps + V2Pipe<R>::P_B, kstep, p.err);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 lds_signal(ps + V2Pipe<R>::P_C);
                 lds_wait(ps + V2Pipe<R>::P_C, W1 * kstep, p.err);
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                // (b) the counters of step k-1 are cleared for step k+1 once every wave is done with them: the cow
-                // waves by P_C, the books wave by P_B (behind it that wave signals only P_K, a launch-long counter).
-                // Step k+1's drone wave touches them only after R_k, which follows this step's F_E and F_H, which
-                // follow this clear.
+                // V2Pipe's clear (b) of the other counter set, for step k+1
                 int* const flp = (kstep & 1) ? flags0 : X.flags1;
                 if (ct < kV2Flags) flp[ct] = 0;
             } else {
@@ -983,16 +446,16 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
     } else if (PIPE && kstep > 0) {
         // the chain state from the previous step's drone wave, through LDS (global memory holds the same values)
         const R* ho = X.ho + tid;
-        pos[0] = ho[0 * 64]; pos[1] = ho[1 * 64]; pos[2] = ho[2 * 64];
+        pos[0] = ho[kRowPos * 64]; pos[1] = ho[(kRowPos + 1) * 64]; pos[2] = ho[(kRowPos + 2) * 64];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) q[c] = ho[(3 + c) * 64];
+        for (int c = 0; c < 4; ++c) q[c] = ho[(kRowQuat + c) * 64];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { v[c] = ho[(7 + c) * 64]; w[c] = ho[(10 + c) * 64]; }
+        for (int c = 0; c < 3; ++c) { v[c] = ho[(kRowVel + c) * 64]; w[c] = ho[(kRowOmega + c) * 64]; }
 #pragma unroll
-        for (int c = 0; c < 9; ++c) pid[c] = ho[(13 + c) * 64];
+        for (int c = 0; c < 9; ++c) pid[c] = ho[(kRowPid + c) * 64];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) ql[c] = ho[(22 + c) * 64];
-        ev_acc = ho[26 * 64];
+        for (int c = 0; c < 4; ++c) ql[c] = ho[(kRowLink + c) * 64];
+        ev_acc = ho[kRowEvalDist * 64];
         n0 = X.hoi[tid]; stepi = X.hoi[64 + tid];
         stale_d = 1;   // the Euler angles of this attitude are computed here (the cow waves' pass stores the cache later)
     } else if (dlane) {
@@ -1001,19 +464,19 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
         n0 = p.envi[0 * E + e0 + dg];
         stale_d = p.stale[e0 + dg];   // this env's Euler cache (written by the last v2 step)
         if (marl) act0 = p.envi[7 * E + e0 + dg];
-        pos[0] = p.drone[0 * DS + di]; pos[1] = p.drone[1 * DS + di]; pos[2] = p.drone[2 * DS + di];
+        pos[0] = p.drone[kRowPos * DS + di]; pos[1] = p.drone[(kRowPos + 1) * DS + di]; pos[2] = p.drone[(kRowPos + 2) * DS + di];
         if constexpr (MIX) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) { pd[c] = p.pos64[c * DS + di]; pos[c] = R(pd[c]); }
         }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) q[c] = p.drone[(3 + c) * DS + di];
+        for (int c = 0; c < 4; ++c) q[c] = p.drone[(kRowQuat + c) * DS + di];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { v[c] = p.drone[(7 + c) * DS + di]; w[c] = p.drone[(10 + c) * DS + di]; }
+        for (int c = 0; c < 3; ++c) { v[c] = p.drone[(kRowVel + c) * DS + di]; w[c] = p.drone[(kRowOmega + c) * DS + di]; }
 #pragma unroll
-        for (int c = 0; c < 9; ++c) pid[c] = p.drone[(13 + c) * DS + di];
+        for (int c = 0; c < 9; ++c) pid[c] = p.drone[(kRowPid + c) * DS + di];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) ql[c] = p.drone[(22 + c) * DS + di];   // Bullet's cached link frame (link_lag)
+        for (int c = 0; c < 4; ++c) ql[c] = p.drone[(kRowLink + c) * DS + di];   // Bullet's cached link frame (link_lag)
         // Euler angles of this quaternion, stored by the previous step (used iff the cache is
         // valid; loaded regardless so the loads issue with the state's, not after the stale flag returns)
 #pragma unroll
@@ -1215,16 +678,16 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 S.dxd[tid] = pd[0]; S.dyd[tid] = pd[1];
             }
 #pragma unroll
-            for (int c = 0; c < 3; ++c) CH_STS(&D[c * DS + di], pos[c]);
+            for (int c = 0; c < 3; ++c) CH_STS(&D[(kRowPos + c) * DS + di], pos[c]);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) CH_STS(&D[(3 + c) * DS + di], q[c]);
+            for (int c = 0; c < 4; ++c) CH_STS(&D[(kRowQuat + c) * DS + di], q[c]);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { CH_STS(&D[(7 + c) * DS + di], v[c]); CH_STS(&D[(10 + c) * DS + di], w[c]); }
+            for (int c = 0; c < 3; ++c) { CH_STS(&D[(kRowVel + c) * DS + di], v[c]); CH_STS(&D[(kRowOmega + c) * DS + di], w[c]); }
 #pragma unroll
-            for (int c = 0; c < 9; ++c) CH_STS(&D[(13 + c) * DS + di], pid[c]);
+            for (int c = 0; c < 9; ++c) CH_STS(&D[(kRowPid + c) * DS + di], pid[c]);
             if (p.link_lag) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) CH_STS(&D[(22 + c) * DS + di], ql[c]);
+                for (int c = 0; c < 4; ++c) CH_STS(&D[(kRowLink + c) * DS + di], ql[c]);
             }
             S.dx[tid] = pos[0]; S.dy[tid] = pos[1]; S.dz[tid] = pos[2];
 #pragma unroll
@@ -1236,15 +699,15 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             // the chain state for the next step's drone wave (every lane its own slots; a reset env's are rewritten
             // below, before P_N)
             R* ho = X.ho + tid;
-            ho[0 * 64] = pos[0]; ho[1 * 64] = pos[1]; ho[2 * 64] = pos[2];
+            ho[kRowPos * 64] = pos[0]; ho[(kRowPos + 1) * 64] = pos[1]; ho[(kRowPos + 2) * 64] = pos[2];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ho[(3 + c) * 64] = q[c];
+            for (int c = 0; c < 4; ++c) ho[(kRowQuat + c) * 64] = q[c];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { ho[(7 + c) * 64] = v[c]; ho[(10 + c) * 64] = w[c]; }
+            for (int c = 0; c < 3; ++c) { ho[(kRowVel + c) * 64] = v[c]; ho[(kRowOmega + c) * 64] = w[c]; }
 #pragma unroll
-            for (int c = 0; c < 9; ++c) ho[(13 + c) * 64] = pid[c];
+            for (int c = 0; c < 9; ++c) ho[(kRowPid + c) * 64] = pid[c];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ho[(22 + c) * 64] = ql[c];
+            for (int c = 0; c < 4; ++c) ho[(kRowLink + c) * 64] = ql[c];
             X.hoi[tid] = n0; X.hoi[64 + tid] = stepi + 1;
         }
         // the own-state row but its Euler angles, which a cow wave computes from S.dq (obs_euler)
@@ -1259,7 +722,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             ev_acc = eval_distance_step(ev_acc, ei[I_SC * G + dg] == 0, px0, py0, pos[0], pos[1]);
             CH_STS(&p.evald[di], ev_acc);
         }
-        if constexpr (PIPE) X.ho[26 * 64 + tid] = ev_acc;
+        if constexpr (PIPE) X.ho[kRowEvalDist * 64 + tid] = ev_acc;
 
         // per-drone reward terms (CattleAviary.py:230-246, 572-679) and neighbour obs (BaseRLAviary.py:303-317)
         int nb1 = -1, nb2 = -1;   // the two nearest drones (kept for a fast reset's terminal observation)
@@ -1674,16 +1137,16 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 if constexpr (PIPE) {
                     // the new episode's body for the next step's chain: what reset_drone_store leaves in global memory
                     R* ho = X.ho + tid;
-                    ho[0 * 64] = R(xd); ho[1 * 64] = R(yd); ho[2 * 64] = R(zd);
-                    ho[3 * 64] = 0; ho[4 * 64] = 0; ho[5 * 64] = 0; ho[6 * 64] = 1;
+                    ho[kRowPos * 64] = R(xd); ho[(kRowPos + 1) * 64] = R(yd); ho[(kRowPos + 2) * 64] = R(zd);
+                    ho[kRowQuat * 64] = 0; ho[(kRowQuat + 1) * 64] = 0; ho[(kRowQuat + 2) * 64] = 0; ho[(kRowQuat + 3) * 64] = 1;
 #pragma unroll
-                    for (int c = 7; c < 13; ++c) ho[c * 64] = 0;
+                    for (int c = kRowVel; c < kRowPid; ++c) ho[c * 64] = 0;
                     if (!p.compat) {
 #pragma unroll
-                        for (int c = 13; c < 22; ++c) ho[c * 64] = 0;
+                        for (int c = kRowPid; c < kRowLink; ++c) ho[c * 64] = 0;
                     }
-                    ho[22 * 64] = 0; ho[23 * 64] = 0; ho[24 * 64] = 0; ho[25 * 64] = 1;
-                    ho[26 * 64] = 0;
+                    ho[kRowLink * 64] = 0; ho[(kRowLink + 1) * 64] = 0; ho[(kRowLink + 2) * 64] = 0; ho[(kRowLink + 3) * 64] = 1;
+                    ho[kRowEvalDist * 64] = 0;
                     X.hoi[tid] = n_new;
                 }
                 reset_drone_store(p, di, xd, yd, zd);
@@ -1710,11 +1173,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             }
         }
         if constexpr (PIPE) {
-            // P_N: the hand-off is final (R_k is known, the reset envs' new bodies are in) -- the other drone wave
-            // starts chain k+1.  A workgroup-scope release: this wave's stores of step k to the drone state and the
-            // observation rows are complete before that wave stores step k+1's to the same addresses.
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            lds_signal(ps + V2Pipe<R>::P_N);
+            X.publish_next();
             if (tid == 0) PTS(5, (long long)clock64());
         }
         // PIPE: the reward's inputs among the env scalars (the early write-back below moves f_* on to their final values)
@@ -1731,11 +1190,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 if (rs) reset_scalars(p, e, f_n, f_sc, f_scA, f_spawn, f_episode, f_active, f_hp, f_prev, f_clock, n_next);
             }
             CH_ENV_WRITE_BACK();
-            // P_B: the env scalars of step k are written back (released at workgroup scope) and this wave reads none
-            // of S.ei, S.prev, S.clock or the cow tables any more: the cow waves may load step k+1's env scalars and
-            // restage those rows.  The books stay open (see P_K).
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            lds_signal(ps + V2Pipe<R>::P_B);
+            X.publish_scalars();
             if (tid == 0) PTS(6, (long long)clock64());
         }
         // ---- behind R (and P_N; PIPE: and P_B): the reward, which nothing before the books' close waits for.
@@ -1758,15 +1213,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 wave_sync();   // the drone lanes' cattle terms, read by the env lanes
             }
         }
-        if constexpr (PIPE) {
-            // P_K of step k-1: the other drone wave has closed its books.  It stored to the addresses this wave stores
-            // to below (reward, term, trunc, metrics, episode records) and owned X.met until then.  (Expected never
-            // to spin: those books closed a whole chain ago.)
-            if (kstep > 0) {
-                lds_wait(ps + V2Pipe<R>::P_K, kstep, p.err);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            }
-        }
+        if constexpr (PIPE) X.await_prev_books(kstep, p.err);   // this wave's output stores and X.met come next
         if (envl && task) {
             const int n = PIPE ? r_n : f_n;
             if constexpr (!marl) {
@@ -1855,10 +1302,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
         }
         if (tid == 0) TS(7, (long long)clock64());
         if constexpr (PIPE) {
-            // P_K: the books of step k are closed -- every output store of this step is released at workgroup scope,
-            // X.met holds the step's rows and this wave is done with S.dcow.
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            lds_signal(ps + V2Pipe<R>::P_K);
+            X.close_books();
             if (tid == 0)
                 PTS(7, (long long)((unsigned long long)clock64() & ((1ull << 62) - 1)) |
                            (long long)((unsigned long long)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3) << 62));
@@ -2020,16 +1464,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
         if (ct == 0) { TS(8, (long long)clock64()); PTS(10, (long long)clock64()); }
         lds_wait(fl + F_D, 1, p.err);
         if (ct == 0) { TS(9, (long long)clock64()); PTS(11, (long long)clock64()); }
-        if constexpr (PIPE) {
-            // P_K: the books of step k-1 are closed.  The pass below is the first thing in this step that overwrites
-            // S.dcow, which that books wave's closest-cow search reads; and since F_H of this step is signalled behind
-            // this wait, every output store of the books of step k follows those of step k-1.  (Expected never to
-            // spin: the books close within a fraction of a step.)
-            if (kstep > 0) {
-                lds_wait(ps + V2Pipe<R>::P_K, kstep, p.err);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            }
-        }
+        if constexpr (PIPE) X.await_prev_books(kstep, p.err);   // the per-cow pass overwrites S.dcow
         skip_now = skip_post;
         for (;;) {   // per cow: distances, winding number, observation entries (the herd centroid is done)
             const int b = grab(fl + C_COWS, 64, skip_post), u = b + lane;

@@ -35,7 +35,7 @@ __device__ __forceinline__ void step2_once(const StepParams<R>* p, int salt, int
 // The instantiation whose step loop is pipelined over two drone waves (configs[3], f64): step k+1's drone chain needs
 // only the bodies after chain k and step k's reset decision, so a second drone wave starts it as soon as R_k is
 // published, while the first still closes the books of step k (reward, metrics, env write-back) -- see V2Pipe and
-// step2_body's ROLE in ch_step_body.h.
+// step2_body's ROLE in ch_step_body.h; the counters that replace the barrier between two steps: V2Pipe, ch_step_sync.h.
 template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, int WPE>
 constexpr bool kMultiPipelined = sizeof(R) == 8 && MODE == 0 && GT == 16 && NT == 4 && MT == 16 && !PHYS && !PW && WPE == 1;
 // n consecutive steps in one launch (ch_step_n); `pd`: the step's parameters in device memory

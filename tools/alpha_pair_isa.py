@@ -1,6 +1,6 @@
 """Diagnostics: fp64 VALU instructions per evaluated alpha pair, from the gfx950 ISA.
 
-Compiles probe kernels that run exactly one piece of the flock's alpha pair evaluation (ch_step_body.h alpha_full_pw ->
+Compiles probe kernels that run exactly one piece of the flock's alpha pair evaluation (ch_step_flock.h alpha_full_pw ->
 ch_device.h pair_terms_n; flockUtils.py:237-258, 327-337) on one value per lane, with the library's flags, and counts
 the instructions of each kernel body minus a load/store skeleton.  The pieces: the pair norm's sqrt, IEEE divisions
 (zx / den, zy / den, sigma_1's z / sqrt), divc (correctly rounded division by a constant), the bump's cos on [0, pi],

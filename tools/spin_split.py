@@ -1,7 +1,7 @@
 """Diagnostics: how much of k_step2's SQ_INSTS_SALU is hand-off spinning.
 
 Two halves:
-  * static (CPU): the instructions of one sleep iteration of the hand-off waits (ch_step_body.h lds_wait: s_sleep 1, an
+  * static (CPU): the instructions of one sleep iteration of the hand-off waits (ch_step_sync.h lds_wait: s_sleep 1, an
     LDS load of the flag, the compare, the loop control), read from configs[3]'s k_step2 in ch_step.hip's gfx950
     device assembly compiled with the library's flags (`--asm`, made once and cached);
   * dynamic (GPU): a diagnostic build (-DCH_COUNT_SPINS, `--build` writes cattleherd/libcattleherd_spins.so) sums the

@@ -164,7 +164,7 @@ def trace(mode, E, n, m, prec, G=None, B=None, steps=4, summary=None):
 
 def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
     """The pipelined step loop of k_step2_multi (configs[3] f64: two drone waves that alternate steps): ch_step_n
-    launches of 8 steps, stamped per step (ch_step_body.h PTS: slot 16 k + i).  Per step k = 2..7, medians over the
+    launches of 8 steps, stamped per step (ch_step_sync.h PTS: slot 16 k + i).  Per step k = 2..7, medians over the
     workgroups, in cycles: R_{k-1} -> chain start k, the chain, D -> H, H -> R, R -> P_B (env scalars written back), R ->
     books closed (P_K), the period R_{k-1} -> R_k; when the cow waves enter step k, how long they wait for P_B and P_C
     of step k-1 ("cow waves in"), for D_k and R_k."""
