@@ -463,6 +463,75 @@ int ch_evaluate_policy(ch_handle* h, const ch_mlp* actor, const ch_eval_table* t
                        int64_t max_steps, int32_t check_every, int64_t first_step_index,
                        int64_t* steps_run, int64_t* remaining, void* stream);
 
+/* ---- On-device policy evaluation for the DTDE (RLlib) driver -------------------------------------------------
+ * Replaces: the reference's DTDEModelPlayback.py workflow and RLlib's evaluation_* metrics (episode_return_mean,
+ * episode_len_mean, per-agent returns) for the shared policy over RLlibMultiAgentWrapper envs: every env steps with
+ * the deterministic action (explore=False on a DiagGaussian: the mean half, unsquashed to the Box(-1, 1) by a clip)
+ * until it has contributed its share of the n episodes (the CTDE table's quota rule), and each counted episode's
+ * per-agent returns and lengths go into a device table.  An episode is what the wrapper makes of it
+ * (marl_wrapper.py:77-119): agents that terminate drop out, the env ends (and auto-resets) once every agent has
+ * terminated, and a truncation ends nothing.  MARL handles with marl_wrapper = 1 only (CH_ERR_UNSUPPORTED for a CTDE
+ * handle and for the bare-dict semantics); both precisions.  All arrays are caller-owned device memory.
+ * RLlib is not installed here: these semantics are restated from its defaults ("parity unpinned" to its source).
+ * Divergence note (the one ch_marl_rollout_collect documents): RLlib's per-agent episodes treat terminated OR
+ * truncated as done; this restatement follows the wrapper's "__all__" rule, under which a truncation does not end
+ * an episode. */
+typedef struct ch_marl_eval_table {
+    int32_t  capacity;      /* C: episode slots per env */
+    int32_t  _pad;
+    int32_t* quota;         /* device [E]: episodes env e contributes: (n + e) / E, the CTDE table's rule */
+    int32_t* count;         /* device [E]: episodes recorded for env e (never exceeds quota) */
+    double*  ep_return;     /* device [E][C]: the sum over agents, in agent order, of agent_return */
+    double*  agent_return;  /* device [E][C][N]: each agent's summed float32 rewards over the steps it was live at the
+                               start of (added in float64 in step order); 0 for agents that never took part */
+    int32_t* ep_length;     /* device [E][C]: env steps of the episode */
+    int32_t* agent_length;  /* device [E][C][N]: steps the agent was live at the start of (>= 1 exactly for
+                               i < the episode's NUM_DRONES) */
+    int32_t* ep_end_step;   /* device [E][C]: the evaluation step index at which it ended */
+    int64_t* remaining;     /* device [1]: sum over e of quota[e] - count[e] */
+    /* the running state of the current episodes */
+    double*  acc_return;    /* device [E][N] */
+    int32_t* acc_length;    /* device [E][N] */
+    int32_t* acc_steps;     /* device [E] */
+    uint8_t* live;          /* device [E][N]: the agent is live at the start of the step about to run / that just ran */
+} ch_marl_eval_table;
+
+/* Start an evaluation of n_eval_episodes episodes: quota[e] = (n_eval_episodes + e) / E, count = 0, every acc_* = 0,
+ * remaining = n_eval_episodes (`live` is ch_marl_eval_mark's).  The slots are not cleared: slot [e][k] is valid for
+ * k < count[e].  CH_ERR_INVALID if n_eval_episodes < 1 or ceil(n_eval_episodes / E) > capacity. */
+int ch_marl_eval_begin(ch_handle* h, const ch_marl_eval_table* table, int32_t n_eval_episodes, void* stream);
+
+/* Before a step: live[e][i] = i < NUM_DRONES(e) && bit i of active_mask(e), read from the handle's env ints -- the
+ * wrapper's self.agents, exactly ch_marl_rollout's agent_mask. */
+int ch_marl_eval_mark(ch_handle* h, const ch_marl_eval_table* table, void* stream);
+
+/* After a ch_step with CH_STEP_AUTORESET on the same stream (io->reward and io->reset_happened are required,
+ * CH_ERR_INVALID otherwise), one thread per env, agents in index order: for every agent with `live` set
+ * acc_return += (double)reward[e][i] and acc_length += 1 (the reward of an agent that is not live is never read into
+ * a sum); acc_steps += 1.  Where reset_happened[e] is set: if count < quota and count < capacity the episode goes
+ * into slot count[e] (agent_return / agent_length = the accumulators, ep_return = their sum in agent order from 0,
+ * ep_length = acc_steps, step_index), the env counts it and `remaining` drops (one integer atomic per wave); in every
+ * ended env, filed or ignored, the accumulators return to 0.  0 <= step_index < 2^31. */
+int ch_marl_eval_record(ch_handle* h, const ch_marl_eval_table* table, const ch_step_io* io, int64_t step_index,
+                        void* stream);
+
+/* The evaluation loop in one call: ch_evaluate_policy's for a MARL handle.  Per step t on `stream`:
+ * ch_policy_forward(policy) on the agents' observations into io->policy_out ([E * N][width], width >= 4; 8 = mean
+ * then log_std is the trained model's); one action kernel that runs the recorder of step t - 1 (between two reads of
+ * `remaining`), marks `live` and writes env_actions[e][i][c] = clamp(policy_out[e * N + i][c], -1, 1), c < 4, for
+ * live agents and 0 for the others; ch_step with auto-reset.  Every check_every steps and at max_steps a stand-alone
+ * recorder runs, `remaining` and the device error word are copied to the host and the stream is synchronised --
+ * nowhere else.  Return codes, *steps_run, *remaining, "reaching max_steps is not an error" and continuation with
+ * first_step_index are ch_evaluate_policy's. */
+typedef struct ch_marl_eval_io {
+    const ch_step_io* step;   /* env step buffers: obs, reward, terminated, truncated, reset_happened */
+    float* policy_out;        /* scratch [E * N][policy->dims[last]] */
+    float* env_actions;       /* scratch [E][N][4] */
+} ch_marl_eval_io;
+int ch_marl_evaluate_policy(ch_handle* h, const ch_mlp* policy, const ch_marl_eval_table* table,
+                            const ch_marl_eval_io* io, int64_t max_steps, int32_t check_every, int64_t first_step_index,
+                            int64_t* steps_run, int64_t* remaining, void* stream);
+
 /* ---- Native PPO minibatch update ---------------------------------------------------------------------------
  * Replaces: stable_baselines3 PPO.train for the CTDE driver's PPO("MlpPolicy", ...) (CTDECattleHerder.py:107-150),
  * one minibatch step at a time: ActorCriticPolicy.evaluate_actions (separate tanh MLPs obs -> pi -> action_net and

@@ -28,9 +28,11 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_mlp_pack", "ch_outputs_to_host", "ch_marl_rollout_collect", "ch_ppo_param_count", "ch_ppo_scratch_size",
            "ch_ppo_grad", "ch_ppo_adam", "ch_ppo_train", "ch_marl_ppo_param_count", "ch_marl_ppo_scratch_size",
            "ch_marl_ppo_grad", "ch_marl_ppo_adam", "ch_marl_ppo_train", "ch_eval_begin", "ch_eval_record",
-           "ch_evaluate_policy")
-# the on-device evaluation's symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
-_EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy")
+           "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark", "ch_marl_eval_record",
+           "ch_marl_evaluate_policy")
+# the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
+_EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
+                 "ch_marl_eval_record", "ch_marl_evaluate_policy")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -115,6 +117,17 @@ class ChEvalIO(ctypes.Structure):
     _fields_ = [("step", ctypes.POINTER(ChStepIO)), ("mean", ctypes.c_void_p), ("env_actions", ctypes.c_void_p)]
 
 
+# the DTDE driver's on-device evaluation (ch_marl_eval_*; cattleherd/marl_eval.py)
+class ChMarlEvalTable(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_int32), ("_pad", ctypes.c_int32)] + \
+        [(k, ctypes.c_void_p) for k in ("quota", "count", "ep_return", "agent_return", "ep_length", "agent_length",
+                                        "ep_end_step", "remaining", "acc_return", "acc_length", "acc_steps", "live")]
+
+
+class ChMarlEvalIO(ctypes.Structure):
+    _fields_ = [("step", ctypes.POINTER(ChStepIO)), ("policy_out", ctypes.c_void_p), ("env_actions", ctypes.c_void_p)]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -183,6 +196,12 @@ def lib():
         L.ch_eval_begin.argtypes = [vp, P(ChEvalTable), i32, vp]
         L.ch_eval_record.argtypes = [vp, P(ChEvalTable), P(ChStepIO), i64, vp]
         L.ch_evaluate_policy.argtypes = [vp, P(ChMlp), P(ChEvalTable), P(ChEvalIO), i64, i32, i64, P(i64), P(i64), vp]
+    if hasattr(L, "ch_marl_evaluate_policy"):
+        L.ch_marl_eval_begin.argtypes = [vp, P(ChMarlEvalTable), i32, vp]
+        L.ch_marl_eval_mark.argtypes = [vp, P(ChMarlEvalTable), vp]
+        L.ch_marl_eval_record.argtypes = [vp, P(ChMarlEvalTable), P(ChStepIO), i64, vp]
+        L.ch_marl_evaluate_policy.argtypes = [vp, P(ChMlp), P(ChMarlEvalTable), P(ChMarlEvalIO), i64, i32, i64, P(i64),
+                                              P(i64), vp]
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in ("ch_step_n",) + _EVAL_EXPORTS or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int

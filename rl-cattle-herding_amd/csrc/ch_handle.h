@@ -1,6 +1,6 @@
 // ch_handle.h — the handle behind the C ABI, private to its host files: ch_api.cpp (config, create / destroy, reset,
-// step, state, metrics, host output), ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection) and
-// ch_api_eval.cpp (the on-device evaluate_policy).
+// step, state, metrics, host output), ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection),
+// ch_api_eval.cpp (the on-device evaluate_policy) and ch_api_marl_eval.cpp (the DTDE driver's evaluation).
 #pragma once
 #include <string>
 #include <vector>
@@ -89,7 +89,7 @@ struct ch_handle {
     std::vector<unsigned char> params_host;   // what d_params holds (uploaded again only when the parameters change)
     ch_rollout_state ro;
     ch_staging st;
-    // ch_evaluate_policy's pinned host copy of {the table's remaining, the device error word} (allocated on first use)
+    // ch_evaluate_policy's and ch_marl_evaluate_policy's pinned host copy of {the table's remaining, the device error word} (allocated on first use)
     long long* eval_host = nullptr;
     // the device error word was reported to the caller (device_status) since it was last cleared
     bool err_seen = false;

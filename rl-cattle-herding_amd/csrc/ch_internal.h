@@ -256,6 +256,33 @@ hipError_t launch_eval_record(const EvalArgs& a, hipStream_t st);
 hipError_t launch_eval_actions(const float* mean, int mean_ld, int act_w, long long E, float* env_actions,
                                const EvalArgs* record_prev, hipStream_t st);
 
+// ch_marl_eval.hip: the DTDE driver's on-device evaluation (ch_marl_eval_*): the per-agent episode table's begin, mark
+// and recorder kernels and the deterministic-action kernel of ch_marl_evaluate_policy
+struct MarlEvalArgs {
+    long long E;
+    int N, C;                  // agents per env, episode slots per env
+    int step_index;
+    int *quota, *count;        // [E]
+    double* ep_return;         // [E][C]
+    double* agent_return;      // [E][C][N]
+    int *ep_length, *agent_length, *ep_end_step;
+    long long* remaining;      // [1]
+    double* acc_return;        // [E][N] the current episodes
+    int *acc_length, *acc_steps;
+    uint8_t* live;             // [E][N]
+    const int* env_n;          // handle envi row 0 (NUM_DRONES) and row 7 (the live-agent mask)
+    const int* env_active;
+    const float* reward;       // the step's reward [E][N]
+    const uint8_t* reset;      // the step's reset_happened [E]
+};
+hipError_t launch_marl_eval_begin(const MarlEvalArgs& a, long long n_eval, hipStream_t st);
+hipError_t launch_marl_eval_mark(const MarlEvalArgs& a, hipStream_t st);
+hipError_t launch_marl_eval_record(const MarlEvalArgs& a, hipStream_t st);
+// mark, and env_actions[e][i][c] = clamp(pol[(e * N + i) * pol_ld + c], -1, 1), c < 4 <= pol_ld, for live agents, 0 for
+// the others; record_prev: first the recorder of the step before, in the same launch
+hipError_t launch_marl_eval_actions(const float* pol, int pol_ld, float* env_actions, const MarlEvalArgs& a,
+                                    bool record_prev, hipStream_t st);
+
 // up to three independent forwards in one launch (ch_policy.hip k_mlp2).  A segment's role folds the rollout
 // store into its last layer's epilogue (ch_rollout_collect): kRoleSample -- the actor's mean becomes the
 // Gaussian sample, its log-probability and the env actions (k_rollout_store's action half); kRoleValue -- the
