@@ -64,7 +64,7 @@ struct StepParams {
     int phase_mask; // diagnostics only: skip phases (1 drones, 2 flock, 4 task, 8 obs) for time attribution
     int G, P;                 // v2: envs per workgroup, cow pairs per env
     const uint16_t* pairs;    // v2: [P] unordered cow pairs (i | j << 8) in tri() order
-    long long* tstamp;        // diagnostics only: [grid][16] per-workgroup phase timestamps (ch__set_tstamp)
+    long long* tstamp;        // diagnostics only: [grid][128] per-workgroup phase timestamps (ch__set_tstamp); [2 grid][128] for ch_step_n (PTSS)
     int physics;              // CH_PHYS_* (v1 kernel only; ch_api.cpp selects v1 for the variants)
     double gnd_h_clip;        // GND_EFF_H_CLIP (BaseAviary.py:173)
     R* phys;                  // [kPhysComps][E][NC]

@@ -334,6 +334,9 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                   "the pipelined step loop is the configs[3] f64 instantiation's");
     static_assert(!PIPE || GT == V2Pipe<R>::kMetG, "X.met holds kMetG envs per metric row");
     constexpr bool marl = MODE == 1;
+    // ENVQ (the pipelined step loop, whose herd is a compile-time 16): the shared alpha queue's cheap pass takes whole
+    // envs (alpha_cheap_env).  Every other instantiation keeps alpha_cheap.
+    constexpr bool ENVQ = PIPE && MT == 16 && !PW;
     // f32 mode: positions, centroids and the approach delta in f64 (StepParams::pos64); PT = their type
     constexpr bool MIX = sizeof(R) == 4;
     using PT = double;
@@ -580,7 +583,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             spin_note(spins);
             co_simd = (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3) + 1 == ds;
         }
-        if (ct == 0) TS(11, (long long)clock64());
+        if (ct == 0) { TS(11, (long long)clock64()); PTSS(0, (long long)clock64()); }
         if (ct < 64) {
             // herd centroid (CattleAviary.py: HerdCentroid, np.mean over the cattle): needs only the integrated
             // cows, so it is done before the drone hand-off (signal HC)
@@ -1419,13 +1422,14 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             tf = S.tdf + (size_t)(tid / 64 - 1) * M * N;
             qu = S.queue + (size_t)(tid / 64 - 1) * P;
         } else {
-            alpha_cheap(S, fl, M, P, nf, flist, skip_pre);
-            if (ct == 0) TS(38, (long long)clock64());
+            if constexpr (ENVQ) alpha_cheap_env<R, GT, MT, MT * (MT - 1) / 2>(S, fl, nf, flist, skip_pre);
+            else alpha_cheap(S, fl, M, P, nf, flist, skip_pre);
+            if (ct == 0) { TS(38, (long long)clock64()); PTSS(1, (long long)clock64()); }
             lds_signal(fl + F_C);
             if (ct == 0) { TS(39, (long long)clock64()); TS(29, (long long)lds_peek(fl + Q_LEN)); }
             alpha_full(S, fl, M, P, skip_pre, W1, p.err);
         }
-        if (ct == 0) TS(18, (long long)clock64());
+        if (ct == 0) { TS(18, (long long)clock64()); PTSS(2, (long long)clock64()); }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int u = ct + k * CW;
@@ -1445,6 +1449,7 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
             // alpha rows while the drone wave still integrates: once every pair is in the table, row chunks
             // are taken until the drone positions arrive; the rest follows the drone hand-off below
             int sleeps = 0;
+            bool row_ts = false;   // (diagnostics: the first row chunk is stamped)
             for (int spins = 0; spins < (1 << 22); ++spins) {
                 if (lds_peek(fl + F_D) >= 1) break;
                 if (lds_peek(fl + F_A) < W1) { __builtin_amdgcn_s_sleep(1); ++sleeps; continue; }
@@ -1452,6 +1457,9 @@ __device__ __forceinline__ void step2_body(const StepParams<R>& p, int salt = 0,
                 const int b = grab(fl + C_ROWS, 64, skip_pre), u = b + lane;
                 if (b >= nf * M) break;
                 CHUNK_T0;
+                if constexpr (PIPE) {
+                    if (ct == 0 && !row_ts) { PTSS(3, (long long)clock64()); row_ts = true; }
+                }
                 if (u < nf * M) {
                     const int f = qdiv(u, M, rM), g = flist[f], j = u - f * M;
                     alpha_row(S, M, P, g * M + j, g, j);

@@ -74,6 +74,65 @@ __device__ __forceinline__ void alpha_cheap(V2Smem<R>& S, int* fl, int M, int P,
     }
 }
 
+// The same pass for the pipelined step loop's geometry (compile-time G, M and P; NC = the pass's 64-pair chunks), one
+// unit per flocking env instead of one per 64 queue positions: C_PAIRS counts envs.  The lane's pair words are read
+// once per step, ahead of the first grab (a pair past P repeats pair 0 and is masked out by r < P), and so is the
+// flock list (lane f holds env f; the unit's env is a readlane); every chunk's position loads are issued before any
+// test, and one returning add on Q_LEN reserves the env's slots, filled in (chunk, lane) order.  A unit is three
+// dependent LDS round trips (grab, positions, reservation) where alpha_cheap's 64-pair chunk is five, and an env is
+// one unit where it was two chunks.  The queue's order differs from alpha_cheap's; nothing read from it depends on
+// the order: the masks are ORs, the pair table is indexed by the pair (gi) and the rows walk the masks in ascending
+// order.
+template <class R, int G, int M, int P>
+__device__ __forceinline__ void alpha_cheap_env(V2Smem<R>& S, int* fl, int nf, const int* flist, bool skip) {
+    constexpr int NC = (P + 63) / 64;
+    static_assert(G <= 64 && (G & (G - 1)) == 0, "the flock list is held one env per lane");
+    const int lane = threadIdx.x & 63;
+    uint32_t prw[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int r = 64 * c + lane;
+        prw[c] = S.pl[r < P ? r : 0];
+    }
+    const int flv = flist[lane & (G - 1)];   // (entries past nf are stale and never selected)
+    for (;;) {
+        const int f = grab(fl + C_PAIRS, 1, skip);
+        if (f >= nf) break;
+        const int g = __builtin_amdgcn_readlane(flv, f & (G - 1));
+        R n2[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const uint32_t pr = prw[c];
+            const int bi = g * M + (pr & 0xff), bj = g * M + (pr >> 8);
+            const R zx = S.cx[bj] - S.cx[bi], zy = S.cy[bj] - S.cy[bi];
+            n2[c] = zx * zx + zy * zy;
+        }
+        bool cand[NC];
+        unsigned long long m[NC];
+        int tot = 0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const uint32_t pr = prw[c];
+            const int li = pr & 0xff, hi = pr >> 8;
+            cand[c] = 64 * c + lane < P && n2[c] <= R(kAlphaSupport2);
+            if (cand[c]) {
+                atomicOr(&S.nbm[g * M + li], 1ull << hi);
+                atomicOr(&S.nbm[g * M + hi], 1ull << li);
+            }
+            m[c] = __ballot(cand[c]);
+            tot += (int)__popcll(m[c]);
+        }
+        int base = 0;
+        if (lane == 0 && tot) base = atomicAdd(fl + Q_LEN, tot);
+        base = __builtin_amdgcn_readfirstlane(base);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (cand[c]) S.queue[base + __popcll(m[c] & ((1ull << lane) - 1ull))] = (uint16_t)(g * P + 64 * c + lane);
+            base += (int)__popcll(m[c]);
+        }
+    }
+}
+
 // The full evaluation of the queued pairs, streamed (the barrier form is in DESIGN_HISTORY.md): a wave
 // that runs out of cheap-pass chunks starts on the queue at once instead of waiting at a pass-wide barrier for
 // the other waves' last cheap chunks.  Every queue slot starts as kQEmpty (phase 0); a chunk of 64 slots is taken

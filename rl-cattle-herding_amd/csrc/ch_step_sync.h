@@ -98,6 +98,10 @@ __device__ __forceinline__ void cow_sync(int* f, int waves, bool global, int* er
 //   12 flock work done, waits for R (first cow wave), 13 the same, latest cow wave, 14 R seen (first cow wave),
 //   15 step end, latest cow wave
 #define PTS(i, val) do { if (PIPE && p.tstamp && kstep < 8) p.tstamp[(long long)blockIdx.x * 128 + 16 * kstep + (i)] = (val); } while (0)
+// The first cow wave's split of "enters step k" .. "waits for D", in a second table behind the first (the pipelined
+// kernel's stamp buffer is [2 grid][128]: row grid + workgroup, slot 16 k + i): 0 staging done (past F_E), 1 its cheap
+// pass done, 2 its full pass done, 3 its first alpha-row chunk taken (0: none before D)
+#define PTSS(i, val) do { if (PIPE && p.tstamp && kstep < 8) p.tstamp[((long long)gridDim.x + blockIdx.x) * 128 + 16 * kstep + (i)] = (val); } while (0)
 #define PTS_MAX(i) do { if (PIPE && p.tstamp && kstep < 8 && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.tstamp + (long long)blockIdx.x * 128 + 16 * kstep + (i)), (unsigned long long)clock64()); } while (0)
 
 // LDS of the pipelined step loop (k_step2_multi, configs[3] f64), placed after the V2Layout carve:

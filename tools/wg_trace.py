@@ -30,7 +30,7 @@ def trace(mode, E, n, m, prec, G=None, B=None, steps=4, summary=None):
     g, blk, lds, kv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
     L.ch__geometry(b.handle, ctypes.byref(g), ctypes.byref(blk), ctypes.byref(lds), ctypes.byref(kv))
     grid = (E + g.value - 1) // g.value
-    ts = torch.zeros((grid, 128), dtype=torch.int64, device=b.device)
+    ts = torch.zeros((2 * grid, 128), dtype=torch.int64, device=b.device)   # (rows grid..: the pipelined kernel's second table)
     b.reset()
     for _ in range(0 if os.environ.get("CH_TRACE_NOBURN") else 250):   # steady state: resets have desynchronised the flocking parity
         b.step(random_actions=True, autoreset=True, terminal_obs=False)
@@ -47,7 +47,7 @@ def trace(mode, E, n, m, prec, G=None, B=None, steps=4, summary=None):
         else:
             b.step(random_actions=True, autoreset=True, terminal_obs=False)
         torch.cuda.synchronize()
-        t = ts.cpu().numpy()
+        t = ts.cpu().numpy()[:grid]
         w0, w1 = t[:, 0], t[:, 1]
         span_us = (w1.max() - w0.min()) / 100.0
         start = (w0 - w0.min()) / 100.0
@@ -167,7 +167,8 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
     launches of 8 steps, stamped per step (ch_step_sync.h PTS: slot 16 k + i).  Per step k = 2..7, medians over the
     workgroups, in cycles: R_{k-1} -> chain start k, the chain, D -> H, H -> R, R -> P_B (env scalars written back), R ->
     books closed (P_K), the period R_{k-1} -> R_k; when the cow waves enter step k, how long they wait for P_B and P_C
-    of step k-1 ("cow waves in"), for D_k and R_k."""
+    of step k-1 ("cow waves in"), for D_k and R_k.  A library that writes the first cow wave's sub-segment stamps (PTSS, the
+    buffer's second table) also gets that wave's staging, cheap pass, full pass and first row chunk."""
     L = _lib.lib()
     b = HerdBatch(E, n, m, mode=mode, precision=prec)
     if G is not None:
@@ -175,7 +176,8 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
     g, blk, lds, kv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
     L.ch__geometry(b.handle, ctypes.byref(g), ctypes.byref(blk), ctypes.byref(lds), ctypes.byref(kv))
     grid = (E + g.value - 1) // g.value
-    ts = torch.zeros((grid, 128), dtype=torch.int64, device=b.device)
+    # two tables: rows 0..grid-1 the per-step stamps, rows grid.. the first cow wave's sub-segment stamps (PTSS)
+    ts = torch.zeros((2 * grid, 128), dtype=torch.int64, device=b.device)
     b.reset()
     for _ in range(0 if os.environ.get("CH_TRACE_NOBURN") else 250):
         b.step(random_actions=True, autoreset=True, terminal_obs=False)
@@ -187,7 +189,9 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
         torch.cuda.synchronize()
         b.step_n(8, random_actions=True)
         torch.cuda.synchronize()
-        t = ts.cpu().numpy().reshape(grid, 8, 16)
+        t = ts.cpu().numpy()[:grid].reshape(grid, 8, 16)
+        u = ts.cpu().numpy()[grid:].reshape(grid, 8, 16)   # all zero: a library from before the sub-segment stamps
+        has_sub = bool((u[:, 2:, :3] > 0).all())
         if not ((t[:, :, 4] > 0).all() and (np.diff(t[:, :, 4], axis=1) > 0).all()):   # R of steps 0..7, in order
             print("   no per-step stamps: this library's kernel is not the pipelined one")
             b.close()
@@ -212,9 +216,20 @@ def trace_pipe(mode, E, n, m, prec, G=None, B=None, launches=4, summary=None):
                  "cow_flock_done_after_D": q50(c[:, 12] - c[:, 11]), "last_cow_flock_done_after_D": q50(c[:, 13] - c[:, 11]),
                  "cow_waits_R": q50(c[:, 14] - c[:, 12]), "cow_end_after_R_k": q50(c[:, 15] - c[:, 4]),
                  "resetting_wgs_prev": int(((c[:, 5] - c[:, 4]) > 400).sum())}
+            if has_sub:
+                # the first cow wave between "in" (slot 9) and "waits for D" (slot 10): staging (to F_E), its cheap
+                # pass, its full pass, the wait for the table (F_A) up to its first row chunk, and the rows up to D
+                d = u[:, k]
+                rw = d[:, 3] > 0
+                r.update({"cow_staging": q50(d[:, 0] - c[:, 9]), "cow_cheap": q50(d[:, 1] - d[:, 0]),
+                          "cow_cheap_done_after_R": q50(d[:, 1] - R0), "cow_full": q50(d[:, 2] - d[:, 1]),
+                          "cow_full_done_after_R": q50(d[:, 2] - R0),
+                          "cow_full_to_first_row": q50(d[rw, 3] - d[rw, 2]) if rw.any() else float("nan"),
+                          "cow_first_row_to_ready": q50(c[rw, 10] - d[rw, 3]) if rw.any() else float("nan"),
+                          "wgs_with_rows_before_D": int(rw.sum())})
             rows.append(r)
             print(f"   step {k}: " + " ".join(f"{a}={v:.0f}" for a, v in r.items()))
-        mean = {a: float(np.mean([r[a] for r in rows])) for a in rows[0]}
+        mean = {a: float(np.nanmean([r[a] for r in rows])) for a in rows[0]}
         print("   mean of steps 2..7: " + " ".join(f"{a}={v:.0f}" for a, v in mean.items()))
         if summary is not None:
             summary.append({"wg_cycles_q50": mean["period_R_to_R"], "chain_cycles_q50": mean["chain"],
@@ -303,7 +318,7 @@ def back_to_back(mode="ctde", E=4096, n=4, m=16, prec="f64", k=12):
     g, blk, lds, kv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
     L.ch__geometry(b.handle, ctypes.byref(g), ctypes.byref(blk), ctypes.byref(lds), ctypes.byref(kv))
     grid = (E + g.value - 1) // g.value
-    ts = torch.zeros((k, grid, 128), dtype=torch.int64, device=b.device)
+    ts = torch.zeros((k, 2 * grid, 128), dtype=torch.int64, device=b.device)
     b.reset()
     for _ in range(250):
         b.step(random_actions=True, autoreset=True, terminal_obs=False)
@@ -313,7 +328,7 @@ def back_to_back(mode="ctde", E=4096, n=4, m=16, prec="f64", k=12):
         b.step(random_actions=True, autoreset=True, terminal_obs=False)
     torch.cuda.synchronize()
     L.ch__set_tstamp(b.handle, None)
-    t = ts.cpu().numpy()
+    t = ts.cpu().numpy()[:, :grid]
     prev_end = None
     for i in range(k):
         w0, w1 = t[i, :, 0].min(), t[i, :, 1].max()
