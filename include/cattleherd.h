@@ -680,6 +680,73 @@ int ch_marl_ppo_train(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp,
                       const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                       float* stats, float* scratch, void* stream);
 
+/* ---- Device-side evaluator log: the per-step rows of update_evaluation_metrics ---------------------------------
+ * Replaces: the reference's logging while is_evaluating is set -- BaseAviary.update_evaluation_metrics (sb3_envs/
+ * BaseAviary.py:1406-1437) and the time-out evaluation_episode_trigger of _computeTruncated (CattleAviary.py:545-548)
+ * -- for a chosen subset of a batch's envs, as a device table: one row per logged env and step, written by a small
+ * kernel after the step, with no host synchronisation and no copy of the state (HerdBatch.get_state is the only other
+ * route to these values).  cattleherd.eval_log turns the table into the reference's evaluation_data.pkl schema.
+ *
+ * THE ONE RESTRICTION: the recorder reads the handle's state, which must be the post-step, pre-reset state.  It
+ * therefore follows a ch_step WITHOUT CH_STEP_AUTORESET; the caller (or ch_eval_log_run) then resets the finished envs
+ * with a masked ch_reset.  With the flag set in the io, ch_eval_log_record returns CH_ERR_INVALID.
+ * CTDE handles only (MARL: CH_ERR_UNSUPPORTED), both precisions (an f32 handle's state is widened exactly: the log is
+ * always float64; positions are the f64 copies ch_get_state returns).  The handle needs cfg.eval_metrics
+ * (CH_ERR_UNSUPPORTED otherwise, as ch_get_eval).  N = cfg.num_drones, M = cfg.num_cattle below.
+ * The env indices of sel_env must be distinct: each logged env's rows are owned by one wave and written with plain
+ * stores, so a duplicate index leaves rows / dropped and the rows of that env undefined. */
+typedef struct ch_eval_log {
+    int32_t n_sel;            /* S: logged envs */
+    int32_t capacity;         /* T: rows per logged env */
+    const int32_t* sel_env;   /* device [S]: env indices, distinct, 0 <= . < E (validated on entry by the caller-facing
+                                 Python; the kernel skips an out-of-range index and sets the handle's error word) */
+    int32_t* rows;            /* device [S]: rows written so far (<= T) */
+    int32_t* dropped;         /* device [S]: steps not logged because the env's rows were full */
+    /* per row [S][T] */
+    double*  time;            /* step_counter at the step's start / ctrl_freq (update_evaluation_metrics' ep_time) */
+    double*  effectiveness;   /* evaluate_herding_effectiveness after the step, in percent */
+    int32_t* num_drones;      /* NUM_DRONES of the episode */
+    int32_t* episode;         /* the env's episode counter (env int `episode`) */
+    uint8_t* flags;           /* bit 0 terminated, bit 1 truncated (the step's outputs), bit 2 time-out trigger:
+                                 ep_time > EPISODE_LEN_SEC and none of _computeTruncated's conditions 1-4 holds
+                                 (CattleAviary.py:513-548) -- where evaluation_episode_trigger fires.  EPISODE_LEN_SEC
+                                 is the handle's (its configured curriculum level's), the value the step's own
+                                 truncation compares with */
+    double*  drone_xy;        /* [S][T][N][2] after the step; 0 for i >= NUM_DRONES */
+    double*  drone_vxy;       /* [S][T][N][2] */
+    double*  drone_dist;      /* [S][T][N]   the evald accumulator after the step */
+    double*  cattle_xy;       /* [S][T][M][2] after the step */
+    double*  cattle_vxy;      /* [S][T][M][2] at the step's START (what the reference's read-back returns) */
+    /* carry, written by ch_eval_log_mark */
+    double*  start_cattle_vxy;/* device [S][M][2] */
+    int32_t* start_counter;   /* device [S] */
+} ch_eval_log;
+/* (drone_xy, drone_vxy, cattle_xy, cattle_vxy and start_cattle_vxy are stored as pairs: 16-byte aligned.) */
+
+/* rows = dropped = 0 for every logged env.  Stream-ordered. */
+int ch_eval_log_begin(ch_handle* h, const ch_eval_log* log, void* stream);
+/* Before a step: the carry (the cattle velocities and step_counter at the step's start) of every logged env. */
+int ch_eval_log_mark(ch_handle* h, const ch_eval_log* log, void* stream);
+/* After a step without CH_STEP_AUTORESET (io: that step's io; terminated and truncated are read): one row per logged
+ * env.  An env whose rows are full increments `dropped` and writes nothing; no row index ever reaches `capacity`,
+ * whatever the arrays hold. */
+int ch_eval_log_record(ch_handle* h, const ch_eval_log* log, const ch_step_io* io, void* stream);
+
+typedef struct ch_eval_log_io {
+    const ch_step_io* step;  /* obs, reward, terminated, truncated; flags must not hold CH_STEP_AUTORESET */
+    float* mean;             /* scratch [E][actor->dims[last]] */
+    float* env_actions;      /* scratch [E][num_drones][4] */
+    uint8_t* done_mask;      /* scratch [E] */
+} ch_eval_log_io;
+/* Replaces: the playback loop `action = model.predict(obs, deterministic=True); env.step(action); env.reset() when
+ * the episode ended` with is_evaluating set, for every env of the batch, n_steps times: ch_policy_forward, the
+ * deterministic action (the clamp ch_evaluate_policy documents), mark, ch_step without auto-reset, record -- which
+ * here also writes done_mask[e] = terminated | truncated for EVERY env -- and ch_reset(done_mask) into step->obs.
+ * No host synchronisation and no host read; a HIP error ends the loop with CH_ERR_DEVICE and nothing further is
+ * launched.  The sticky device error word is not read here: the caller's ch_sync reports it. */
+int ch_eval_log_run(ch_handle* h, const ch_mlp* actor, const ch_eval_log* log, const ch_eval_log_io* io,
+                    int64_t n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

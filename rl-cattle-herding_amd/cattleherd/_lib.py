@@ -29,10 +29,11 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_ppo_grad", "ch_ppo_adam", "ch_ppo_train", "ch_marl_ppo_param_count", "ch_marl_ppo_scratch_size",
            "ch_marl_ppo_grad", "ch_marl_ppo_adam", "ch_marl_ppo_train", "ch_eval_begin", "ch_eval_record",
            "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark", "ch_marl_eval_record",
-           "ch_marl_evaluate_policy")
+           "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark", "ch_eval_log_record", "ch_eval_log_run")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
-                 "ch_marl_eval_record", "ch_marl_evaluate_policy")
+                 "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
+                 "ch_eval_log_record", "ch_eval_log_run")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -128,6 +129,19 @@ class ChMarlEvalIO(ctypes.Structure):
     _fields_ = [("step", ctypes.POINTER(ChStepIO)), ("policy_out", ctypes.c_void_p), ("env_actions", ctypes.c_void_p)]
 
 
+# the device-side evaluator log (ch_eval_log_*; cattleherd/eval_log.py)
+class ChEvalLog(ctypes.Structure):
+    _fields_ = [("n_sel", ctypes.c_int32), ("capacity", ctypes.c_int32)] + \
+        [(k, ctypes.c_void_p) for k in ("sel_env", "rows", "dropped", "time", "effectiveness", "num_drones", "episode",
+                                        "flags", "drone_xy", "drone_vxy", "drone_dist", "cattle_xy", "cattle_vxy",
+                                        "start_cattle_vxy", "start_counter")]
+
+
+class ChEvalLogIO(ctypes.Structure):
+    _fields_ = [("step", ctypes.POINTER(ChStepIO)), ("mean", ctypes.c_void_p), ("env_actions", ctypes.c_void_p),
+                ("done_mask", ctypes.c_void_p)]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -202,6 +216,11 @@ def lib():
         L.ch_marl_eval_record.argtypes = [vp, P(ChMarlEvalTable), P(ChStepIO), i64, vp]
         L.ch_marl_evaluate_policy.argtypes = [vp, P(ChMlp), P(ChMarlEvalTable), P(ChMarlEvalIO), i64, i32, i64, P(i64),
                                               P(i64), vp]
+    if hasattr(L, "ch_eval_log_run"):
+        L.ch_eval_log_begin.argtypes = [vp, P(ChEvalLog), vp]
+        L.ch_eval_log_mark.argtypes = [vp, P(ChEvalLog), vp]
+        L.ch_eval_log_record.argtypes = [vp, P(ChEvalLog), P(ChStepIO), vp]
+        L.ch_eval_log_run.argtypes = [vp, P(ChMlp), P(ChEvalLog), P(ChEvalLogIO), i64, vp]
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in ("ch_step_n",) + _EVAL_EXPORTS or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int

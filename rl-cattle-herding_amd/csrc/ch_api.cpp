@@ -204,7 +204,10 @@ int device_status(ch_handle* h, int word) {
                 "device error word " + std::to_string(word) +
                     ((word & CH_DEVERR_HANDOFF) ? ": a step kernel's LDS hand-off timed out (ch_step_sync.h lds_wait); "
                                                   "the results of that step are wrong"
-                                                : ""));
+                                                : "") +
+                    ((word & CH_DEVERR_LOG_INDEX) ? ": an evaluator log's sel_env held an env index outside [0, E); "
+                                                    "that entry was not logged"
+                                                  : ""));
 }
 
 extern "C" {

@@ -1,6 +1,7 @@
 // ch_handle.h — the handle behind the C ABI, private to its host files: ch_api.cpp (config, create / destroy, reset,
 // step, state, metrics, host output), ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection),
-// ch_api_eval.cpp (the on-device evaluate_policy) and ch_api_marl_eval.cpp (the DTDE driver's evaluation).
+// ch_api_eval.cpp (the on-device evaluate_policy), ch_api_marl_eval.cpp (the DTDE driver's evaluation) and
+// ch_api_eval_log.cpp (the device-side evaluator log).
 #pragma once
 #include <string>
 #include <vector>

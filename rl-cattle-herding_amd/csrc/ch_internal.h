@@ -85,6 +85,7 @@ struct StepParams {
 
 // device error word bits (ch_api.cpp reports them as CH_ERR_DEVICE)
 constexpr int CH_DEVERR_HANDOFF = 1;       // a v2 LDS hand-off wait ran out of spins (ch_step_sync.h lds_wait)
+constexpr int CH_DEVERR_LOG_INDEX = 2;     // an evaluator log's sel_env held an index outside [0, E) (ch_eval_log.hip)
 // diagnostics phase_mask bits beyond 1/2/4/8 (skip drones / flock / task / obs)
 constexpr int CH_PHASE_FORCE_TIMEOUT = 64; // test only: the drone wave waits for a hand-off that never comes
 
@@ -255,6 +256,36 @@ hipError_t launch_eval_record(const EvalArgs& a, hipStream_t st);
 // record_prev (optional): first the recorder of the step before, in the same launch
 hipError_t launch_eval_actions(const float* mean, int mean_ld, int act_w, long long E, float* env_actions,
                                const EvalArgs* record_prev, hipStream_t st);
+
+// ch_eval_log.hip: the device-side evaluator log (ch_eval_log_*): the table of include/cattleherd.h ch_eval_log, the
+// handle's state it reads, and the outputs of the step it follows
+struct EvalLogArgs {
+    long long E;
+    int NC, M;                 // the handle's num_drones, num_cattle
+    int S, T;                  // logged envs, rows per logged env
+    int ctrl_freq;
+    double episode_len;        // the handle's EPISODE_LEN_SEC (StepParams::episode_len)
+    // the handle's SoA state (StepParams): R = double or float by the handle's precision; pos64 / cpos64 in f32 mode
+    const void *drone, *cattle;
+    const double *pos64, *cpos64;
+    const int* envi;
+    const double* evald;
+    int* err;
+    // the table
+    const int* sel;
+    int *rows, *dropped;
+    double *time, *eff;
+    int *num_drones, *episode;
+    uint8_t* flags;
+    double *drone_xy, *drone_vxy, *drone_dist, *cattle_xy, *cattle_vxy, *start_vxy;
+    int* start_counter;
+    // record: the step's terminated / truncated [E]; done_mask (optional, ch_eval_log_run) [E]
+    const uint8_t *term, *trunc;
+    uint8_t* done_mask;
+};
+hipError_t launch_eval_log_begin(const EvalLogArgs& a, hipStream_t st);
+hipError_t launch_eval_log_mark(const EvalLogArgs& a, bool f32, hipStream_t st);
+hipError_t launch_eval_log_record(const EvalLogArgs& a, bool f32, hipStream_t st);
 
 // ch_marl_eval.hip: the DTDE driver's on-device evaluation (ch_marl_eval_*): the per-agent episode table's begin, mark
 // and recorder kernels and the deterministic-action kernel of ch_marl_evaluate_policy
