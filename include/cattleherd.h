@@ -360,6 +360,43 @@ int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* 
                        const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
                        int32_t bootstrap_truncated, void* stream);
 
+/* ---- Device-side SB3 training log: the episode ring (rollout/ep_rew_mean, rollout/ep_len_mean) ---------------
+ * Replaces: OnPolicyAlgorithm._update_info_buffer, which appends Monitor's info["episode"] of every env that ended an
+ * episode to ep_info_buffer = deque(maxlen=stats_window_size), step by step and in env order inside collect_rollouts;
+ * the logger's rollout/ep_rew_mean and rollout/ep_len_mean are the means over that deque.  Here the deque is a ring of
+ * `window` slots in device memory, appended to by one small kernel after each step, with no host synchronisation.
+ * CTDE handles only (CH_ERR_UNSUPPORTED for a MARL handle).  All arrays are caller-owned device memory.
+ * (SB3 is not installed here: restated from its source, "parity unpinned".) */
+typedef struct ch_ep_ring {
+    int32_t  window;      /* W >= 1: SB3's stats_window_size (100) */
+    int32_t  _pad;
+    double*  ep_return;   /* device [W]: io->episode_stats[e][0], as it is (no rounding on the device) */
+    int32_t* ep_length;   /* device [W]: io->episode_stats[e][1] */
+    int32_t* ep_env;      /* device [W]: the env it came from */
+    int64_t* total;       /* device [1]: episodes appended since begin; episode k lives in slot k % W */
+} ch_ep_ring;
+
+/* total = 0 (the slots are not cleared: the ring holds episodes max(0, total - W) .. total - 1). */
+int ch_ep_ring_begin(ch_handle* h, const ch_ep_ring* ring, void* stream);
+
+/* After a ch_step with CH_STEP_AUTORESET on the same stream (io->reset_happened and io->episode_stats are required,
+ * CH_ERR_INVALID otherwise; nothing else of the io and nothing of the handle but n_envs is read): the C envs with
+ * reset_happened[e] != 0 are appended in ascending env order, the order _update_info_buffer walks `infos` -- the
+ * env of rank r among them is episode total + r and goes to slot (total + r) % W; when C > W only the last W of the
+ * step (r >= C - W) are written, so that every slot has one writer; then total += C.  One workgroup: a counting
+ * pass and a ranking pass (wave ballots and a scan of the wave totals) over the envs in chunks of 1024; plain stores,
+ * no atomics.  n_envs up to 262144 and beyond. */
+int ch_ep_ring_record(ch_handle* h, const ch_ep_ring* ring, const ch_step_io* io, void* stream);
+
+/* ch_rollout_collect with the episode ring: with ring != NULL, ch_ep_ring_record runs once per step, right after the
+ * launch that holds step t's env step (ch_step, or the step fused with the next step's actor forward) and before
+ * anything that can overwrite reset_happened or episode_stats, on every path of the collection; io->step->episode_stats
+ * is then required (CH_ERR_INVALID).  ring == NULL is ch_rollout_collect exactly.  The rollout buffer's contents do
+ * not depend on the ring.  The call does not begin the ring: one ring spans the collections of a training run. */
+int ch_rollout_collect_log(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
+                           const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
+                           int32_t bootstrap_truncated, const ch_ep_ring* ring, void* stream);
+
 /* ---- On-device rollout collection for the DTDE (RLlib) driver ----------------------------------------------
  * Replaces: RLlib PPO's sampling of RLlibMultiAgentWrapper envs with one shared policy over every agent
  * (DTDECattleHerder.py:62-97: policies = {"shared_policy"}, gamma 0.99, train_batch_size 4096; the wrapper's
@@ -603,6 +640,32 @@ int ch_ppo_adam(const ch_ppo_net* net, const ch_ppo_hparams* hp, const float* gr
 int ch_ppo_train(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
                  int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
                  void* stream);
+
+/* ch_ppo_train with SB3's two per-minibatch diagnostics (PPO.train's approx_kl_divs and clip_fractions), from the
+ * values the loss already holds: log_ratio = log_prob - old_log_prob, ratio = exp(log_ratio),
+ *   approx_kl = mean((ratio - 1) - log_ratio), clip_fraction = mean(|ratio - 1| > clip_range),
+ * summed per 16-row tile in row order and over the tiles in index order (rows past the minibatch add 0): the same
+ * state gives the same bits.  clip_fraction tests the loss's own float32 ratio.  approx_kl's row term cancels (it is
+ * ~log_ratio^2 / 2), so it alone is evaluated in float64 -- the log-probability summed again from the same float32
+ * mean, then expm1(log_ratio) - log_ratio -- and rounded once to float32.
+ * stats is required: [steps][CH_PPO_LOG_STATS], columns 0-3 what ch_ppo_train writes into [steps][4] from the same
+ * state, then approx_kl, clip_fraction.  The weights, m, v and the step count are what ch_ppo_train leaves. */
+#define CH_PPO_LOG_STATS 6   /* policy loss, value loss, mean entropy, grad norm, approx_kl, clip_fraction */
+int ch_ppo_train_log(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
+                     int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats,
+                     float* scratch, void* stream);
+
+/* Replaces: stable_baselines3.common.utils.explained_variance(rollout_buffer.values.flatten(),
+ * rollout_buffer.returns.flatten()), PPO.train's train/explained_variance.  Handle-free; errors through
+ * ch_last_error(NULL).  out_dev[0] = 1 - var(returns - values) / var(returns) with population variances (np.var), NaN
+ * when var(returns) == 0; out_dev[1] = var(returns).  Float64 and two-pass: the means first, then the squared
+ * deviations; workgroup partials are combined in index order (no atomics: the same input gives the same bits).
+ * DIFFERENCE: SB3 computes this in float32 numpy; here the float32 inputs are widened exactly and every sum is
+ * float64.  values, returns: device [n], n >= 1; out_dev: device double [2]; scratch: device,
+ * ch_explained_variance_scratch(n) doubles (host only; -1 for n < 1). */
+int64_t ch_explained_variance_scratch(int64_t n);
+int ch_explained_variance(const float* values, const float* returns, int64_t n, double* out_dev, double* scratch,
+                          void* stream);
 
 /* ---- Native PPO minibatch update for the DTDE (RLlib) driver's shared policy ---------------------------------
  * Replaces: the minibatch step of RLlib 2.x's new-API-stack PPO learner (PPOTorchLearner.compute_loss_for_module,

@@ -29,11 +29,17 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_ppo_grad", "ch_ppo_adam", "ch_ppo_train", "ch_marl_ppo_param_count", "ch_marl_ppo_scratch_size",
            "ch_marl_ppo_grad", "ch_marl_ppo_adam", "ch_marl_ppo_train", "ch_eval_begin", "ch_eval_record",
            "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark", "ch_marl_eval_record",
-           "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark", "ch_eval_log_record", "ch_eval_log_run")
+           "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark", "ch_eval_log_record", "ch_eval_log_run",
+           "ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
+           "ch_explained_variance_scratch", "ch_explained_variance")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
                  "ch_eval_log_record", "ch_eval_log_run")
+# the SB3 training log's symbols (cattleherd/train_log.py): an older library lacks them too
+_TRAIN_LOG_EXPORTS = ("ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
+                      "ch_explained_variance_scratch", "ch_explained_variance")
+CH_PPO_LOG_STATS = 6   # ch_ppo_train_log's columns: policy loss, value loss, mean entropy, grad norm, approx_kl, clip_fraction
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -142,6 +148,12 @@ class ChEvalLogIO(ctypes.Structure):
                 ("done_mask", ctypes.c_void_p)]
 
 
+# the SB3 training log's episode ring (ch_ep_ring_*; cattleherd/train_log.py)
+class ChEpRing(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_int32), ("_pad", ctypes.c_int32)] + \
+        [(k, ctypes.c_void_p) for k in ("ep_return", "ep_length", "ep_env", "total")]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -221,12 +233,20 @@ def lib():
         L.ch_eval_log_mark.argtypes = [vp, P(ChEvalLog), vp]
         L.ch_eval_log_record.argtypes = [vp, P(ChEvalLog), P(ChStepIO), vp]
         L.ch_eval_log_run.argtypes = [vp, P(ChMlp), P(ChEvalLog), P(ChEvalLogIO), i64, vp]
+    if hasattr(L, "ch_ep_ring_record"):
+        L.ch_ep_ring_begin.argtypes = [vp, P(ChEpRing), vp]
+        L.ch_ep_ring_record.argtypes = [vp, P(ChEpRing), P(ChStepIO), vp]
+        L.ch_ppo_train_log.argtypes = L.ch_ppo_train.argtypes
+        L.ch_explained_variance_scratch.argtypes = [i64]
+        L.ch_explained_variance.argtypes = [vp, vp, i64, vp, vp, vp]
     for name in EXPORTS:
-        if name not in ("ch_last_error",) and (name not in ("ch_step_n",) + _EVAL_EXPORTS or hasattr(L, name)):
+        if name not in ("ch_last_error",) and (name not in ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int
     L.ch_mlp_packed_size.restype = ctypes.c_int64
     L.ch_ppo_param_count.restype = L.ch_ppo_scratch_size.restype = ctypes.c_int64
     L.ch_marl_ppo_param_count.restype = L.ch_marl_ppo_scratch_size.restype = ctypes.c_int64
+    if hasattr(L, "ch_explained_variance_scratch"):
+        L.ch_explained_variance_scratch.restype = ctypes.c_int64
     _lib = L
     return L
 

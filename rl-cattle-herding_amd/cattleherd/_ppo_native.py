@@ -65,18 +65,19 @@ class NativeState:
         self.step_count = torch.zeros(1, dtype=torch.int64, device=model.device)
         self.scratch = None
 
-    def train(self, hp, data, n_epochs, n, batch_size, draw, stats=None):
+    def train(self, hp, data, n_epochs, n, batch_size, draw, stats=None, log=False):
         """``n_epochs`` calls of the flavour's ``*_train`` on the current stream of the model's device, each over the
         ``n`` row indices (int64, on the device) that ``draw()`` returns, in minibatches of ``batch_size``.  ``hp`` and
         ``data`` are the flavour's hparams and data structs; ``stats``: None or the per-step statistics' float32
-        tensor ``[n_epochs * steps per epoch, k]``.  Returns the number of minibatch steps."""
+        tensor ``[n_epochs * steps per epoch, k]``.  ``log`` (SB3 flavour): ``*_train_log``, whose ``stats`` are
+        required and ``CH_PPO_LOG_STATS`` wide.  Returns the number of minibatch steps."""
         import torch
         lib, dev = _lib.lib(), self.model.device
         net = net_struct(self.fl, self.model)   # the parameters' storage as it is now (a .to() or .data = ... moves it)
         want = getattr(lib, self.fl.prefix + "scratch_size")(ctypes.byref(net), min(batch_size, n))
         if self.scratch is None or self.scratch.numel() < want:
             self.scratch = torch.empty(want, dtype=torch.float32, device=dev)
-        train = getattr(lib, self.fl.prefix + "train")
+        train = getattr(lib, self.fl.prefix + ("train_log" if log else "train"))
         nb = (n + batch_size - 1) // batch_size
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream

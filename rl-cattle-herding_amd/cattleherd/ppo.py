@@ -10,7 +10,7 @@ optimizer step is seen by the next collection (``DevicePolicy`` re-packs before 
 restates SB3 2.x ``PPO.train``: ``n_epochs`` passes over a fresh permutation of the buffer in minibatches of
 ``batch_size``, per-minibatch advantage normalisation, the clipped surrogate, MSE value loss, entropy bonus, Adam
 (eps 1e-5, SB3's ActorCriticPolicy default), ``clip_grad_norm_``.  SB3 is not installed: parity unpinned to its
-source (no logging statistics, and the permutation comes from torch's generator, not NumPy's).
+source (the permutation comes from torch's generator, not NumPy's).
 
 With ``graph=True`` each run of ``steps_per_graph`` minibatch steps is one captured HIP graph (static index buffer,
 capturable Adam): the update of a 64-row minibatch is ~60 small kernels, so launch overhead, not arithmetic, is
@@ -19,11 +19,15 @@ what an eager loop would measure.
 ``backend="native"`` (or ``CH_PPO_BACKEND=native``) runs the same minibatch sequence through ``ch_ppo_train``
 (csrc/ch_ppo.hip): forward, loss, backward, ``clip_grad_norm_`` and Adam as three hand-written launches per step, on
 the parameters' own storage.  The default stays ``"torch"``.
+
+``log_stats=True`` (native backend) makes ``train`` also fill ``last_log`` with SB3's ``train/`` logger keys, from
+device-side data read once at the end: ``ch_ppo_train_log``'s per-minibatch ``approx_kl`` and ``clip_fraction`` beside
+the losses, and the buffer's explained variance (``train_log.explained_variance``, float64 where SB3 is float32).
 """
 import math
 import os
 
-from . import _ppo_native
+from . import _lib, _ppo_native
 from ._lib import ChPpoData, ChPpoHparams, ChPpoNet, lib as _bind  # noqa: F401  (the structs' and the binding's old home)
 
 
@@ -105,17 +109,27 @@ def ppo_net(model):
 class PPOUpdate:
     """SB3 ``PPO.train`` over a ``DeviceRolloutBuffer`` (defaults: the CTDE driver's hyper-parameters).
     ``backend``: ``"torch"`` (autograd, optionally graph-captured) or ``"native"`` (``ch_ppo_train``); ``None`` reads
-    ``CH_PPO_BACKEND`` (default ``"torch"``).  The native backend ignores ``graph``."""
+    ``CH_PPO_BACKEND`` (default ``"torch"``).  The native backend ignores ``graph``.  ``log_stats`` (native backend
+    only, ``ValueError`` with torch): ``train`` fills ``last_log`` with SB3's ten ``train/`` keys and ``last_stats``
+    with the raw per-minibatch statistics ``[steps, 6]`` (ch_ppo_train_log's columns) they were computed from."""
+
+    LOG_KEYS = ("train/entropy_loss", "train/policy_gradient_loss", "train/value_loss", "train/approx_kl",
+                "train/clip_fraction", "train/loss", "train/explained_variance", "train/std", "train/n_updates",
+                "train/clip_range")
 
     def __init__(self, model, learning_rate=3e-4, n_epochs=10, batch_size=64, clip_range=0.1, ent_coef=0.1,
                  vf_coef=0.7, max_grad_norm=0.5, normalize_advantage=True, graph=True, steps_per_graph=32, seed=0,
-                 backend=None):
+                 backend=None, log_stats=False):
         torch = _torch()
         if backend is None:
             backend = os.environ.get("CH_PPO_BACKEND", "torch")
         if backend not in ("torch", "native"):
             raise ValueError(f"PPOUpdate backend must be 'torch' or 'native', not {backend!r}")
         self.backend = backend
+        self.log_stats = bool(log_stats)
+        if self.log_stats and backend != "native":
+            raise ValueError("PPOUpdate log_stats=True needs backend='native' (the statistics are ch_ppo_train_log's)")
+        self.last_log, self.last_stats, self.n_updates = {}, None, 0
         if backend == "native":
             graph = False
             self._native = _ppo_native.NativeState(_ppo_native.SB3, model)   # raises for a model it cannot take
@@ -211,7 +225,7 @@ class PPOUpdate:
         nb = (n + bs - 1) // bs
         steps = 0
         if self.backend == "native":
-            return self._train_native(data, n, nb)
+            return self._train_native(data, n, nb, rb)
         for _ in range(self.n_epochs):
             perm = torch.randperm(n, device=self.model.device, generator=self.gen)
             full = n // bs
@@ -230,17 +244,51 @@ class PPOUpdate:
         self.sgd_steps += steps
         return steps
 
-    def _train_native(self, data, n, nb):
-        """The same permutations as the torch path, one ch_ppo_train call per epoch on the current stream."""
+    def _train_native(self, data, n, nb, rb):
+        """The same permutations as the torch path, one ch_ppo_train (log_stats: ch_ppo_train_log) call per epoch on
+        the current stream."""
         torch = _torch()
         dev = self.model.device
         for t in data:
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                 raise ValueError("native PPO update: the rollout buffer must be contiguous float32 on the model's device")
+        stats = None
+        if self.log_stats:
+            stats = torch.zeros((self.n_epochs * nb, _lib.CH_PPO_LOG_STATS), dtype=torch.float32, device=dev)
         steps = self._native.train(self._hp, ChPpoData(*(t.data_ptr() for t in data), n), self.n_epochs, n,
-                                   self.batch_size, lambda: torch.randperm(n, device=dev, generator=self.gen))
+                                   self.batch_size, lambda: torch.randperm(n, device=dev, generator=self.gen),
+                                   stats=stats, log=self.log_stats)
         self.sgd_steps += steps
+        self.n_updates += self.n_epochs
+        if self.log_stats:
+            self._fill_log(stats, rb)
         return steps
+
+    def _fill_log(self, stats, rb):
+        """SB3 ``PPO.train``'s logger record from the call's statistics, the buffer's explained variance and the
+        current ``log_std``: everything is gathered on the device and read once."""
+        import numpy as np
+        from .train_log import explained_variance
+        torch = _torch()
+        ev = explained_variance(rb.values.view(-1), rb.returns.view(-1))
+        std = torch.exp(self.model.log_std.data).mean().double().view(1)
+        host = torch.cat([stats.double().view(-1), ev, std]).cpu().numpy()      # the one read
+        st = host[:stats.numel()].reshape(stats.shape)
+        pl, vl, ent, akl, cf = st[:, 0], st[:, 1], st[:, 2], st[:, 4], st[:, 5]
+        self.last_stats = st.astype(np.float32)   # (exact: the values were float32)
+        # SB3: each list holds the minibatches' float32 .item()s; the logger records np.mean of each (float64)
+        self.last_log = {
+            "train/entropy_loss": float(np.mean(-ent)),
+            "train/policy_gradient_loss": float(np.mean(pl)),
+            "train/value_loss": float(np.mean(vl)),
+            "train/approx_kl": float(np.mean(akl)),
+            "train/clip_fraction": float(np.mean(cf)),
+            "train/loss": float(pl[-1] + self.ent_coef * -ent[-1] + self.vf_coef * vl[-1]),   # the last minibatch's
+            "train/explained_variance": float(host[stats.numel()]),
+            "train/std": float(host[-1]),
+            "train/n_updates": self.n_updates,
+            "train/clip_range": self.clip_range,
+        }
 
     # Adam's moments over the flat parameters and its step count (native backend)
     exp_avg = property(lambda self: self._native.exp_avg)

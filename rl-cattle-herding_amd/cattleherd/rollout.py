@@ -40,6 +40,9 @@ def _bind():
                                        ctypes.POINTER(L.ChMlp), vp, u64, f32, f32, i32, vp]
     for f in (lib.ch_rollout_store, lib.ch_rollout_post, lib.ch_rollout_gae, lib.ch_rollout_collect):
         f.restype = ctypes.c_int
+    if hasattr(lib, "ch_rollout_collect_log"):   # (an older library, e.g. an A/B baseline loaded through CH_LIB_PATH, lacks it)
+        lib.ch_rollout_collect_log.argtypes = lib.ch_rollout_collect.argtypes[:-1] + [ctypes.POINTER(L.ChEpRing), vp]
+        lib.ch_rollout_collect_log.restype = ctypes.c_int
     return lib
 
 
@@ -70,12 +73,14 @@ class DeviceRolloutBuffer:
         self._rb = rb
         self._lib = _bind()
 
-    def collect(self, actor, critic, log_std, seed=0, bootstrap_truncated=True):
+    def collect(self, actor, critic, log_std, seed=0, bootstrap_truncated=True, ring=None):
         """SB3 collect_rollouts for n_steps steps of every env, on the device, in one native call
         (ch_rollout_collect: the loop of collect_steps below runs in C++).  ``actor``: DevicePolicy of the
         action mean (no clip: SB3's action_net output), ``critic``: DevicePolicy of V, ``log_std``:
         float32 [act_dim] device tensor.  ``critic=None``: ``actor`` is a fused actor-critic
-        (DevicePolicy.sb3_actor_critic / fuse, output [mean, value]) and one forward per step serves both."""
+        (DevicePolicy.sb3_actor_critic / fuse, output [mean, value]) and one forward per step serves both.
+        ``ring``: a ``train_log.EpisodeRing`` of this batch; every step's ended episodes are appended to it in env
+        order (ch_rollout_collect_log: one small launch more per step; the buffer's contents do not depend on it)."""
         b, lib = self.batch, self._lib
         torch = b.torch
         log_std = log_std.to(device=b.device, dtype=torch.float32).contiguous()
@@ -95,20 +100,26 @@ class DeviceRolloutBuffer:
             io.mean, io.value = self.mean.data_ptr(), self.value.data_ptr()
             io.terminal_value = self.terminal_value.data_ptr()
         io.env_actions = self.env_actions.data_ptr()
-        keep = b._io.terminal_obs
+        if ring is not None and ring.batch is not b:
+            raise ValueError("the episode ring belongs to another batch")
+        keep = b._io.terminal_obs, b._io.reset_happened, b._io.episode_stats
         b._io.terminal_obs = b.terminal_obs.data_ptr()
+        b._io.reset_happened, b._io.episode_stats = b.reset_happened.data_ptr(), b.episode_stats.data_ptr()
+        args = (b.handle, ctypes.byref(self._rb), ctypes.byref(io), ctypes.byref(actor._net),
+                None if critic is None else ctypes.byref(critic._net), log_std.data_ptr(), int(seed), self.gamma,
+                self.gae_lambda, int(bool(bootstrap_truncated)))
         try:
-            L.check(lib.ch_rollout_collect(b.handle, ctypes.byref(self._rb), ctypes.byref(io), ctypes.byref(actor._net),
-                                           None if critic is None else ctypes.byref(critic._net), log_std.data_ptr(),
-                                           int(seed), self.gamma, self.gae_lambda, int(bool(bootstrap_truncated)),
-                                           b._stream()), b.handle)
+            if ring is None:
+                L.check(lib.ch_rollout_collect(*args, b._stream()), b.handle)
+            else:
+                L.check(lib.ch_rollout_collect_log(*args, ctypes.byref(ring._ring), b._stream()), b.handle)
         finally:
-            b._io.terminal_obs = keep
+            b._io.terminal_obs, b._io.reset_happened, b._io.episode_stats = keep
         return self
 
-    def collect_steps(self, actor, critic, log_std, seed=0, bootstrap_truncated=True):
+    def collect_steps(self, actor, critic, log_std, seed=0, bootstrap_truncated=True, ring=None):
         """The same collection driven from Python one kernel at a time (the reference loop the native
-        call restates; kept for the parity test)."""
+        call restates; kept for the parity test).  ``ring``: as in ``collect`` (``ring.record()`` after each step)."""
         b, lib, rb = self.batch, self._lib, ctypes.byref(self._rb)
         torch = b.torch
         log_std = log_std.to(device=b.device, dtype=torch.float32).contiguous()
@@ -119,6 +130,8 @@ class DeviceRolloutBuffer:
                                          log_std.data_ptr(), int(seed), self.env_actions.data_ptr(), b._stream()),
                     b.handle)
             b.step(self.env_actions, autoreset=True, terminal_obs=True)
+            if ring is not None:
+                ring.record()
             tv = None
             if bootstrap_truncated:
                 # V(terminal obs) only for the envs that just reset (the only rows ch_rollout_post reads)

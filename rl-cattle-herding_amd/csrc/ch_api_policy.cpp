@@ -280,9 +280,10 @@ int ch_rollout_gae(ch_handle* h, const ch_rollout* rb, const float* last_value, 
     return CH_OK;
 }
 
-int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
-                       const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
-                       int32_t bootstrap_truncated, void* stream) {
+// ch_rollout_collect and ch_rollout_collect_log (`ring`: NULL, or the episode ring each step's ended episodes go to)
+static int rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
+                           const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
+                           int32_t bootstrap_truncated, const ch_ep_ring* ring, void* stream) {
     RolloutArgs ra;
     int rc = rollout_args(h, rb, ra, "ch_rollout_collect");
     if (rc) return rc;
@@ -293,6 +294,8 @@ int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* 
         (bootstrap_truncated && !io->terminal_value))
         return fail(h, CH_ERR_INVALID, "ch_rollout_collect: the step buffers (obs, reward, terminated, truncated, "
                                        "terminal_obs, reset_happened) and terminal_value are required");
+    EpRingArgs er;   // the recorder's arguments: the ring and this io's reset_happened / episode_stats
+    if (ring && (rc = ep_ring_args(h, ring, sio, er, "ch_rollout_collect_log"))) return rc;
     if (!rb->obs || !rb->actions || !rb->rewards || !rb->episode_starts || !rb->values || !rb->log_probs ||
         !rb->advantages || !rb->returns || !rb->last_episode_starts)
         return fail(h, CH_ERR_INVALID, "ch_rollout_collect: NULL rollout buffer array");
@@ -416,6 +419,11 @@ int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* 
         } else if ((rc = ch_step(h, &s, stream))) {
             return rc;
         }
+        // The episode ring: step t's reset_happened / episode_stats are written by the launch above on every path
+        // (the fused one runs step t's env step, then step t + 1's actor forward) and by nothing else before step
+        // t + 1's env step: the forwards, the store, the flush and the post write the buffer, the queue and the
+        // scratch outputs only.  So the recorder goes right here.
+        if (ring) HIP_TRY(h, launch_ep_ring_record(er, st));
     }
     // The tail: the last step's post (and queue) with the last flush, V(obs after the last step) = GAE's last_value,
     // GAE.  The epilogue path posts before that forward, the others after it and only when bootstrapping -- without
@@ -437,6 +445,18 @@ int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* 
     a.gamma_lambda = (float)((double)gamma * (double)gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
     HIP_TRY(h, launch_rollout(a, 2, st));
     return CH_OK;
+}
+
+int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
+                       const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
+                       int32_t bootstrap_truncated, void* stream) {
+    return rollout_collect(h, rb, io, actor, critic, log_std, seed, gamma, gae_lambda, bootstrap_truncated, nullptr, stream);
+}
+
+int ch_rollout_collect_log(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
+                           const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
+                           int32_t bootstrap_truncated, const ch_ep_ring* ring, void* stream) {
+    return rollout_collect(h, rb, io, actor, critic, log_std, seed, gamma, gae_lambda, bootstrap_truncated, ring, stream);
 }
 
 int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,

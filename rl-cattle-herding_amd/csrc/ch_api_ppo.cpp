@@ -211,12 +211,14 @@ int adam(const typename F::Net* net, const typename F::Hparams* hp, const float*
     return e == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
 }
 
+// log_stats (Sb3: ch_ppo_train_log): `stats` is required and CH_PPO_LOG_STATS wide, with approx_kl and clip_fraction
 template <class F>
 int train(const typename F::Net* net, const typename F::Hparams* hp, const typename F::Data* data, const int64_t* idx,
           int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
-          void* stream) {
-    const std::string w = who<F>("train");
-    if (!net || !hp || !data || !idx || !m || !v || !step_dev || !scratch) return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
+          void* stream, bool log_stats = false) {
+    const std::string w = who<F>(log_stats ? "train_log" : "train");
+    if (!net || !hp || !data || !idx || !m || !v || !step_dev || !scratch || (log_stats && !stats))
+        return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
     PpoNet n;
     PpoData d;
     std::string err;
@@ -230,6 +232,7 @@ int train(const typename F::Net* net, const typename F::Hparams* hp, const typen
     hipStream_t st = (hipStream_t)stream;
     float* grad = scratch + s.grad;
     long long* step = reinterpret_cast<long long*>(step_dev);
+    const int n_stats = log_stats ? CH_PPO_LOG_STATS : ppo_n_stats(F::kFlavour);
     int64_t k = 0;
     for (int64_t j = 0; j < n_idx; j += batch_size, ++k) {
         const int64_t batch = std::min(batch_size, n_idx - j);
@@ -237,9 +240,9 @@ int train(const typename F::Net* net, const typename F::Hparams* hp, const typen
         sj.tiles = (int)((batch + kPpoTile - 1) / kPpoTile);
         sj.bp = sj.tiles * kPpoTile;
         int np = 0;
-        hipError_t e = ppo_launch_grad(n, h, d, reinterpret_cast<const long long*>(idx) + j, batch, grad, scratch, sj, step, &np, st);
+        hipError_t e = ppo_launch_grad(n, h, d, reinterpret_cast<const long long*>(idx) + j, batch, grad, scratch, sj, step, &np, st, log_stats);
         if (e == hipSuccess)
-            e = ppo_launch_adam(n, h, grad, m, v, step, scratch, sj, np, batch, stats ? stats + ppo_n_stats(F::kFlavour) * k : nullptr, st);
+            e = ppo_launch_adam(n, h, grad, m, v, step, scratch, sj, np, batch, stats ? stats + n_stats * k : nullptr, st, log_stats);
         if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
     }
     return CH_OK;
@@ -266,6 +269,12 @@ int ch_ppo_train(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_d
                  int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
                  void* stream) {
     return train<Sb3>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
+}
+
+int ch_ppo_train_log(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
+                     int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
+                     void* stream) {
+    return train<Sb3>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream, true);
 }
 
 int64_t ch_marl_ppo_param_count(const ch_marl_ppo_net* net) { return param_count<Rllib>(net); }

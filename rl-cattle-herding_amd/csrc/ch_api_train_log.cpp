@@ -1,0 +1,67 @@
+// ch_api_train_log.cpp — the SB3 training log's part of the C ABI (see include/cattleherd.h): the episode ring
+// (ch_ep_ring_begin, ch_ep_ring_record; its wiring into the collection is ch_rollout_collect_log in ch_api_policy.cpp)
+// and the handle-free ch_explained_variance.  Kernels in ch_ep_ring.hip; ch_ppo_train_log lives with ch_ppo_train in
+// ch_api_ppo.cpp.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+
+#include "ch_handle.h"
+
+using namespace ch;
+
+// the ring first (it can be judged without a handle), then the handle, then the step io
+int ep_ring_args(ch_handle* h, const ch_ep_ring* ring, const ch_step_io* io, EpRingArgs& a, const char* who) {
+    if (!ring) return fail(h, CH_ERR_INVALID, std::string(who) + ": NULL ring");
+    if (ring->window < 1) return fail(h, CH_ERR_INVALID, std::string(who) + ": the ring's window must be >= 1");
+    if (!ring->ep_return || !ring->ep_length || !ring->ep_env || !ring->total)
+        return fail(h, CH_ERR_INVALID, std::string(who) + ": every ring array is required");
+    if (!h) return fail(nullptr, CH_ERR_INVALID, std::string(who) + ": NULL handle");
+    if (h->cfg.mode != CH_MODE_CTDE)
+        return fail(h, CH_ERR_UNSUPPORTED, std::string(who) + ": the episode ring is for CTDE handles");
+    std::memset(&a, 0, sizeof(a));
+    a.E = h->E; a.W = ring->window;
+    a.ep_return = ring->ep_return; a.ep_length = ring->ep_length; a.ep_env = ring->ep_env;
+    a.total = reinterpret_cast<long long*>(ring->total);
+    if (io) {
+        if (!io->reset_happened || !io->episode_stats)
+            return fail(h, CH_ERR_INVALID, std::string(who) + ": the step io must carry reset_happened and episode_stats");
+        a.reset = io->reset_happened; a.stats = io->episode_stats;
+    }
+    return CH_OK;
+}
+
+extern "C" {
+
+int ch_ep_ring_begin(ch_handle* h, const ch_ep_ring* ring, void* stream) {
+    EpRingArgs a;
+    if (int rc = ep_ring_args(h, ring, nullptr, a, "ch_ep_ring_begin")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemsetAsync(a.total, 0, sizeof(long long), (hipStream_t)stream));
+    return CH_OK;
+}
+
+int ch_ep_ring_record(ch_handle* h, const ch_ep_ring* ring, const ch_step_io* io, void* stream) {
+    EpRingArgs a;
+    if (!io) return fail(h, CH_ERR_INVALID, "ch_ep_ring_record: NULL step io");
+    if (int rc = ep_ring_args(h, ring, io, a, "ch_ep_ring_record")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, launch_ep_ring_record(a, (hipStream_t)stream));
+    return CH_OK;
+}
+
+int64_t ch_explained_variance_scratch(int64_t n) {
+    if (n < 1) { fail(nullptr, CH_ERR_INVALID, "ch_explained_variance_scratch: n < 1"); return -1; }
+    return ev_scratch_doubles(n);
+}
+
+int ch_explained_variance(const float* values, const float* returns, int64_t n, double* out_dev, double* scratch,
+                          void* stream) {
+    if (!values || !returns || !out_dev || !scratch) return fail(nullptr, CH_ERR_INVALID, "ch_explained_variance: NULL argument");
+    if (n < 1) return fail(nullptr, CH_ERR_INVALID, "ch_explained_variance: n < 1");
+    const hipError_t e = launch_explained_variance(values, returns, n, out_dev, scratch, (hipStream_t)stream);
+    return e == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, std::string("ch_explained_variance launch: ") + hipGetErrorString(e));
+}
+
+}  // extern "C"

@@ -1,0 +1,151 @@
+// ch_ep_ring.hip -- the device side of the SB3 training log (include/cattleherd.h ch_ep_ring_*, ch_explained_variance):
+// the episode ring behind rollout/ep_rew_mean and rollout/ep_len_mean, and train/explained_variance.
+//
+// Reference: OnPolicyAlgorithm._update_info_buffer appends Monitor's info["episode"] of every env that ended an episode
+// to a deque(maxlen=stats_window_size), in env order, after each step of collect_rollouts; PPO.train logs
+// explained_variance(values.flatten(), returns.flatten()).  (SB3 is not installed here: restated, "parity unpinned".)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "ch_internal.h"
+
+namespace ch {
+
+// ---- the episode ring ------------------------------------------------------------------------------------------
+// One workgroup.  C, the number of envs that ended in the step, decides who writes (only the last W of the step), so
+// the envs are walked twice: a counting pass, then the ranking pass of k_stage_ended (ch_aux.hip) -- each chunk of
+// 1024 envs ranked by wave ballots and a scan of the 16 wave totals, so that the ranks follow the env order.  Episode
+// total + r goes to slot (total + r) % W; with r >= C - W every slot has exactly one writer: plain stores.
+constexpr int kRingThreads = 1024;
+constexpr int kRingWaves = kRingThreads / 64;
+
+__global__ __launch_bounds__(kRingThreads) void k_ep_ring_record(EpRingArgs a) {
+    __shared__ long long wsum[kRingWaves + 1];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const long long total = *a.total;   // (rewritten by thread 0 at the very end, behind the barriers below)
+    // the counting pass: each wave's count over its lanes' envs, then the waves in index order
+    long long mine = 0;
+    for (long long c0 = 0; c0 < a.E; c0 += kRingThreads) {
+        const long long e = c0 + t;
+        mine += __popcll(__ballot(e < a.E && a.reset[e] != 0));   // (the same in every lane of the wave)
+    }
+    if (lane == 0) wsum[w] = mine;
+    __syncthreads();
+    long long C = 0;
+    for (int k = 0; k < kRingWaves; ++k) C += wsum[k];
+    __syncthreads();
+    if (C == 0) return;   // (uniform: most steps end no episode)
+    const long long first = C > a.W ? C - a.W : 0;   // ranks below it would be overwritten within this step
+    long long base = 0;
+    for (long long c0 = 0; c0 < a.E; c0 += kRingThreads) {
+        const long long e = c0 + t;
+        const bool f = e < a.E && a.reset[e] != 0;
+        const unsigned long long m = __ballot(f);
+        if (lane == 0) wsum[w] = __popcll(m);
+        __syncthreads();
+        if (t == 0) {
+            long long s = 0;
+            for (int k = 0; k < kRingWaves; ++k) { const long long v = wsum[k]; wsum[k] = s; s += v; }
+            wsum[kRingWaves] = s;
+        }
+        __syncthreads();
+        if (f) {
+            const long long r = base + wsum[w] + __popcll(m & ((1ull << lane) - 1ull));
+            if (r >= first) {
+                const long long slot = (total + r) % a.W;   // 0 <= slot < W
+                a.ep_return[slot] = a.stats[2 * e];
+                a.ep_length[slot] = (int)a.stats[2 * e + 1];
+                a.ep_env[slot] = (int)e;
+            }
+        }
+        base += wsum[kRingWaves];
+        __syncthreads();
+    }
+    if (t == 0) *a.total = total + C;
+}
+
+hipError_t launch_ep_ring_record(const EpRingArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_ep_ring_record, dim3(1), dim3(kRingThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---- explained variance ----------------------------------------------------------------------------------------
+// y = returns, d = returns - values, both widened exactly to float64.  Three launches, one per all-to-all seam (no
+// atomics): the sums of y and d per workgroup; their means (every workgroup adds the partials in index order) and the
+// squared deviations per workgroup; the final sums and the two outputs.  Within a workgroup thread t adds its
+// elements in order and a fixed LDS tree adds the threads (k_metrics_reduce's scheme): the same input, the same bits.
+constexpr int kEvThreads = 256;
+constexpr int kEvMaxGrid = 256;
+constexpr long long kEvPerGroup = 4096;   // elements per workgroup before the grid stops growing
+
+int ev_grid(long long n) { return (int)std::min<long long>(kEvMaxGrid, (n + kEvPerGroup - 1) / kEvPerGroup); }
+long long ev_scratch_doubles(long long n) { return 4LL * ev_grid(n); }
+
+namespace {
+
+// the workgroup's two sums in thread 0 (sy[0], sd[0])
+__device__ __forceinline__ void ev_tree(double* sy, double* sd, double y, double d) {
+    const int t = threadIdx.x;
+    sy[t] = y; sd[t] = d;
+    __syncthreads();
+    for (int w = kEvThreads / 2; w > 0; w >>= 1) {
+        if (t < w) { sy[t] += sy[t + w]; sd[t] += sd[t + w]; }
+        __syncthreads();
+    }
+}
+
+// workgroup g owns the elements [g * per, min(n, (g + 1) * per))
+__global__ __launch_bounds__(kEvThreads) void k_ev_pass(const float* __restrict__ values, const float* __restrict__ returns,
+                                                        long long n, long long per, double* scratch, int second) {
+    __shared__ double sy[kEvThreads], sd[kEvThreads];
+    __shared__ double mean[2];
+    const int t = threadIdx.x, G = gridDim.x;
+    if (second) {
+        if (t == 0) {
+            double y = 0.0, d = 0.0;
+            for (int g = 0; g < G; ++g) { y += scratch[2 * g]; d += scratch[2 * g + 1]; }
+            mean[0] = y / (double)n; mean[1] = d / (double)n;
+        }
+        __syncthreads();
+    }
+    const double my = second ? mean[0] : 0.0, md = second ? mean[1] : 0.0;
+    const long long lo = (long long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    double y = 0.0, d = 0.0;
+    for (long long i = lo + t; i < hi; i += kEvThreads) {
+        const double r = (double)returns[i], dv = r - (double)values[i];
+        if (second) { y += (r - my) * (r - my); d += (dv - md) * (dv - md); }
+        else { y += r; d += dv; }
+    }
+    ev_tree(sy, sd, y, d);
+    if (t == 0) {
+        double* out = scratch + (second ? 2 * G : 0) + 2 * blockIdx.x;
+        out[0] = sy[0]; out[1] = sd[0];
+    }
+}
+
+__global__ void k_ev_final(const double* scratch, int G, long long n, double* out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double y = 0.0, d = 0.0;
+    for (int g = 0; g < G; ++g) { y += scratch[2 * G + 2 * g]; d += scratch[2 * G + 2 * g + 1]; }
+    const double var_y = y / (double)n, var_d = d / (double)n;
+    out[0] = var_y == 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : 1.0 - var_d / var_y;
+    out[1] = var_y;
+}
+
+}  // namespace
+
+hipError_t launch_explained_variance(const float* values, const float* returns, long long n, double* out, double* scratch,
+                                     hipStream_t st) {
+    const int G = ev_grid(n);
+    const long long per = (n + G - 1) / G;
+    for (int second = 0; second < 2; ++second) {
+        hipLaunchKernelGGL(k_ev_pass, dim3(G), dim3(kEvThreads), 0, st, values, returns, n, per, scratch, second);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_ev_final, dim3(1), dim3(64), 0, st, scratch, G, n, out);
+    return hipGetLastError();
+}
+
+}  // namespace ch

@@ -257,6 +257,22 @@ hipError_t launch_eval_record(const EvalArgs& a, hipStream_t st);
 hipError_t launch_eval_actions(const float* mean, int mean_ld, int act_w, long long E, float* env_actions,
                                const EvalArgs* record_prev, hipStream_t st);
 
+// ch_ep_ring.hip: the SB3 training log's device side: the episode ring's recorder (ch_ep_ring_record) and the
+// explained variance of the rollout buffer (ch_explained_variance)
+struct EpRingArgs {
+    long long E;
+    int W;                     // the ring's slots
+    const uint8_t* reset;      // the step's reset_happened [E]
+    const double* stats;       // the step's episode_stats [E][2]
+    double* ep_return;         // [W]
+    int *ep_length, *ep_env;   // [W]
+    long long* total;          // [1]
+};
+hipError_t launch_ep_ring_record(const EpRingArgs& a, hipStream_t st);
+long long ev_scratch_doubles(long long n);   // n >= 1
+hipError_t launch_explained_variance(const float* values, const float* returns, long long n, double* out, double* scratch,
+                                     hipStream_t st);
+
 // ch_eval_log.hip: the device-side evaluator log (ch_eval_log_*): the table of include/cattleherd.h ch_eval_log, the
 // handle's state it reads, and the outputs of the step it follows
 struct EvalLogArgs {

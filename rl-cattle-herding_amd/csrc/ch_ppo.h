@@ -63,8 +63,10 @@ struct PpoData {
 
 // Scratch (floats) for minibatches of up to `batch` rows, rows padded to whole tiles (bp):
 //   per net: act[l] [bp][dims[l + 1]] hidden activations (l < n_hidden), dz[l] [bp][dims[l + 1]] (every layer)
-//   tile_stat [tiles][2]   sums of the surrogate minimum and of the squared value error
-//             (kPpoRllib: [tiles][4], with the sums of the rows' entropies and KL divergences)
+//   tile_stat [tiles][2]   sums of the surrogate minimum and of the squared value error; with log_stats then
+//             [tiles][2] the sums of SB3's diagnostics (ratio - 1) - log_ratio (evaluated in float64, rounded
+//             once) and |ratio - 1| > clip_range, behind the current minibatch's tiles (kPpoRllib: [tiles][4],
+//             with the sums of the rows' entropies and KL divergences)
 //   tile_dls  [tiles][act] log_std gradient partials (kPpoSb3)
 //   misc      [4]          mean entropy (kPpoSb3)
 //   partial   [workgroups] sum-of-squares partials of the gradient, one per workgroup that produced a piece of it
@@ -76,19 +78,21 @@ struct PpoScratch {
 void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s);
 
 // the three launches of one minibatch step.  ppo_launch_grad: forward, loss and backward per (row tile, net), then the
-// weight-gradient grid; `bump_step` makes the latter increment *step_dev (the Adam step this gradient is for).
+// weight-gradient grid; `bump_step` makes the latter increment *step_dev (the Adam step this gradient is for);
+// log_stats (kPpoSb3): the forward-backward kernel's variant that also leaves the tiles' sums of SB3's two diagnostics.
 // ppo_launch_sumsq: the sum-of-squares partials of a given flat gradient (ch_ppo_adam), increments *step_dev.
 // ppo_launch_adam: every workgroup sums the partials in order, forms the clip coefficient and updates its slice;
-// workgroup 0 writes the step's statistics (ppo_n_stats of them) to `stats` when it is not NULL.  ppo_launch_stats: the
-// statistics alone (ch_ppo_grad, ch_marl_ppo_grad).
+// workgroup 0 writes the step's statistics (ppo_n_stats of them) to `stats` when it is not NULL; log_stats (kPpoSb3):
+// CH_PPO_LOG_STATS of them, with approx_kl and clip_fraction (ch_ppo_train_log).  ppo_launch_stats: the statistics
+// alone (ch_ppo_grad, ch_marl_ppo_grad).
 hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
                            float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
-                           hipStream_t st);
+                           hipStream_t st, bool log_stats = false);
 hipError_t ppo_launch_sumsq(const PpoNet& n, const float* grad, float* scratch, const PpoScratch& s, long long* step_dev,
                             int* n_partials, hipStream_t st);
 hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, float* m, float* v,
                            const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                           float* stats, hipStream_t st);
+                           float* stats, hipStream_t st, bool log_stats = false);
 hipError_t ppo_launch_stats(const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
                             float* stats, hipStream_t st);
 

@@ -18,7 +18,9 @@
 // The three kernels take a compile-time flavour (ch_ppo.h).  kPpoRllib is the minibatch step of RLlib's PPO learner for
 // the DTDE driver's shared policy (cattleherd/marl_ppo.py restates it): the head is [mean, raw log_std], the loss adds
 // the KL penalty against the gathered old dist inputs and clips the value error, k_ppo_dw has no log_std workgroup and
-// k_ppo_adam a no-clip mode and five statistics.  kPpoSb3 is the step described above, unchanged.
+// k_ppo_adam a no-clip mode and five statistics.  kPpoSb3 is the step described above; for
+// ch_ppo_train_log a third k_ppo_fb instantiation (kFbSb3Log) also leaves per-tile sums of SB3's two diagnostics
+// (approx_kl, clip_fraction), which k_ppo_adam turns into two more statistics.
 //
 // MFMA operand map (16x16x4 f32): lane l gives A[row l & 15][k slot l >> 4] and B[k slot l >> 4][col l & 15]; it
 // holds C/D[row 4 (l >> 4) + r][col l & 15] in register r.  Which k a slot stands for is free as long as A and B
@@ -43,6 +45,7 @@ constexpr int kLdo = kPpoMaxAct + 4;     // of the head's output
 constexpr int kDwWaves = 4;              // k_ppo_dw: 256 threads, 64 input columns per wave
 constexpr int kDwCols = 64 * kDwWaves;
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;   // log(sqrt(2 pi))
+constexpr double kHalfLog2Pi64 = 0.91893853320467274178;
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -150,8 +153,13 @@ struct FbArgs {
 template <int F>
 constexpr int kStat = F == kPpoRllib ? 4 : 2;
 
+// k_ppo_fb's third flavour (ch_ppo_train_log): kPpoSb3 plus the per-tile sums of SB3's two diagnostics.  A kernel of
+// its own, so that ch_ppo_train's carries none of the float64 code.
+constexpr int kFbSb3Log = 2;
+
 template <int F>
 __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
+    [[maybe_unused]] constexpr bool kLog = F == kFbSb3Log;
     __shared__ __align__(16) float hs[2][kPpoTile * kLdh];   // hidden activations
     __shared__ __align__(16) float dzs[kPpoTile * kLdh];     // dZ of the last hidden layer
     __shared__ __align__(16) float os[kPpoTile * kLdo];      // the head's output, then its dZ
@@ -290,21 +298,44 @@ __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
                 const bool valid = row0 + row < a.batch;
                 const long long src = a.idx[min(row0 + row, a.batch - 1)];
                 float lp = 0.0f;
+                // (lp64, kFbSb3Log: the same log-probability from the same float32 mean, widened exactly and summed in
+                // float64, for approx_kl alone -- see below; the loss keeps the float32 one)
+                double lp64 = 0.0;
                 for (int j = sub; j < NO; j += 16) {
                     const float ls = a.n.log_std[j], dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
                     lp += -(dlt * dlt) / (2.0f * expf(2.0f * ls)) - ls - kHalfLog2Pi;
+                    if constexpr (kLog) {
+                        const double ls64 = ls, d64 = (double)a.d.actions[src * NO + j] - (double)os[row * kLdo + j];
+                        lp64 += -(d64 * d64) / (2.0 * exp(2.0 * ls64)) - ls64 - kHalfLog2Pi64;
+                    }
                 }
 #pragma unroll
-                for (int o = 8; o > 0; o >>= 1) lp += __shfl_xor(lp, o);
+                for (int o = 8; o > 0; o >>= 1) {
+                    lp += __shfl_xor(lp, o);
+                    if constexpr (kLog) lp64 += __shfl_xor(lp64, o);
+                }
                 float adv = a.d.advantages[src];
                 if (a.normalize && B > 1) adv = (adv - adv_mean) * adv_scale;
-                const float ratio = expf(lp - a.d.old_log_prob[src]);
+                const float log_ratio = lp - a.d.old_log_prob[src];
+                const float ratio = expf(log_ratio);
                 const float s1 = adv * ratio;
                 const float s2 = adv * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
                 // torch.min's gradient goes to the smaller branch (both when they tie: inside the clip range, where the
                 // clamp passes it on); the clamped branch outside the range has none
                 const float dlp = valid && s1 <= s2 ? -inv_b * adv * ratio : 0.0f;
-                if (sub == 0) rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
+                if (sub == 0) {
+                    rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
+                    if constexpr (kLog) {
+                        // SB3's diagnostics of the row (PPO.train's approx_kl_divs and clip_fractions), in the two
+                        // columns of `tmp` past the widest head: (ratio - 1) - log_ratio, and |ratio - 1| > clip_range
+                        // as 0 / 1.  The first cancels: it is ~log_ratio^2 / 2, so the float32 rounding of a
+                        // log-probability of magnitude 10-20 and of the ratio is ~1e-5 of it in a one-row minibatch.
+                        // It is evaluated in float64 from lp64 and rounded once; the clip test is the loss's own ratio.
+                        const double lr64 = lp64 - (double)a.d.old_log_prob[src];
+                        tmp[row * kLdo + kPpoMaxAct] = valid ? (float)(expm1(lr64) - lr64) : 0.0f;
+                        tmp[row * kLdo + kPpoMaxAct + 1] = valid && fabsf(ratio - 1.0f) > a.clip_range ? 1.0f : 0.0f;
+                    }
+                }
                 for (int j = sub; j < NO; j += 16) {
                     const float var = expf(2.0f * a.n.log_std[j]);
                     const float dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
@@ -324,6 +355,15 @@ __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
             float s = 0.0f;
             for (int r = 0; r < kPpoTile; ++r) s += rowstat[r];
             a.scratch[a.s.tile_stat + 2 * tile + ni] = s;
+            if (kLog && ni == 0) {   // the tile's diagnostics, rows in order, behind the [tiles][2] loss partials
+                float kl = 0.0f, cf = 0.0f;
+                for (int r = 0; r < kPpoTile; ++r) {
+                    kl += tmp[r * kLdo + kPpoMaxAct];
+                    cf += tmp[r * kLdo + kPpoMaxAct + 1];
+                }
+                a.scratch[a.s.tile_stat + 2 * a.s.tiles + 2 * tile] = kl;
+                a.scratch[a.s.tile_stat + 2 * a.s.tiles + 2 * tile + 1] = cf;
+            }
             if (ni == 0 && tile == 0) {
                 float e = 0.0f;
                 for (int j = 0; j < NO; ++j) e += 0.5f + kHalfLog2Pi + a.n.log_std[j];
@@ -521,7 +561,8 @@ struct AdamArgs {
     const float* misc;
     int tiles;
     long long batch;
-    int update;           // 0: statistics only
+    int update;           // 0: statistics only; kPpoSb3: bit 1 set = stats4 is [CH_PPO_LOG_STATS], with approx_kl and
+                          // clip_fraction (ch_ppo_train_log)
 };
 
 template <int F>
@@ -552,6 +593,15 @@ __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
         } else {
             a.stats4[2] = a.misc[0];
             a.stats4[3] = norm;
+            if (a.update & 2) {   // the tiles' diagnostics in index order (k_ppo_fb wrote them behind the loss partials)
+                float akl = 0.0f, cf = 0.0f;
+                for (int t = 0; t < a.tiles; ++t) {
+                    akl += a.tile_stat[2 * a.tiles + 2 * t];
+                    cf += a.tile_stat[2 * a.tiles + 2 * t + 1];
+                }
+                a.stats4[4] = akl / (float)a.batch;
+                a.stats4[5] = cf / (float)a.batch;
+            }
         }
     }
     if (!a.update) return;
@@ -612,7 +662,7 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s) {
             s.dz[ni][li] = take((long long)s.bp * m.dims[li + 1]);
         }
     }
-    s.tile_stat = take((n.flavour == kPpoRllib ? 4LL : 2LL) * s.tiles);
+    s.tile_stat = take(4LL * s.tiles);
     s.tile_dls = take(n.flavour == kPpoSb3 ? (long long)s.tiles * n.act_dim : 0);
     s.misc = take(4);
     s.partial = take(std::max(dw_workgroups(n), kSumsqGrid));
@@ -622,7 +672,7 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s) {
 
 hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
                            float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
-                           hipStream_t st) {
+                           hipStream_t st, bool log_stats) {
     FbArgs f;
     std::memset(&f, 0, sizeof(f));
     f.n = n; f.d = d; f.idx = idx; f.batch = batch; f.scratch = scratch; f.s = s;
@@ -634,7 +684,8 @@ hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, c
     for (int ni = 0; ni < 2; ++ni)
         for (int li = 0; li < n.net[ni].layers; ++li) f.vec_w[ni][li] = n.net[ni].dims[li] % 4 == 0 && aligned16(n.net[ni].w[li]);
     const bool rllib = n.flavour == kPpoRllib;
-    hipLaunchKernelGGL(rllib ? k_ppo_fb<kPpoRllib> : k_ppo_fb<kPpoSb3>, dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
+    hipLaunchKernelGGL(rllib ? k_ppo_fb<kPpoRllib> : log_stats ? k_ppo_fb<kFbSb3Log> : k_ppo_fb<kPpoSb3>,
+                       dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
@@ -692,12 +743,12 @@ static void adam_common(AdamArgs& a, const PpoNet& n, float* scratch, const PpoS
 
 hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, float* m, float* v,
                            const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                           float* stats, hipStream_t st) {
+                           float* stats, hipStream_t st, bool log_stats) {
     AdamArgs a;
     adam_common(a, n, scratch, s, n_partials, batch, stats);
     a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
     a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
-    a.update = 1;
+    a.update = log_stats && n.flavour == kPpoSb3 ? 3 : 1;
     const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
     hipLaunchKernelGGL(n.flavour == kPpoRllib ? k_ppo_adam<kPpoRllib> : k_ppo_adam<kPpoSb3>, dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError();

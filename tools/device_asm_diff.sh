@@ -41,6 +41,8 @@ for f in $(cmds "$(pwd)" | cut -d' ' -f1); do
     echo "$f: identical but for the unit id ($(grep -c '^\s*\.amdhsa_kernel ' "$s") kernels, $(wc -l < "$s") lines)"
   else
     echo "$f: DIFFERS"; rc=1
+    # which of its kernels do: a change may edit some instantiations of a file and must leave the others alone
+    python3 -B "$(dirname "$0")/device_asm_kernels.py" "$s" "$OUT/other/$f.s" | sed 's/^/    /'
   fi
 done
 [ -n "${KEEP:-}" ] || rm -rf "$OUT"
