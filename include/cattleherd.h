@@ -442,6 +442,62 @@ typedef struct ch_marl_rollout_io {
 int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
                             const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream);
 
+/* ---- Device-side RLlib training log: the episode ring of a MARL handle (env_runners/...) ----------------------
+ * Replaces: what RLlib's env runners report of RLlibMultiAgentWrapper envs while the DTDE driver trains
+ * (DTDECattleHerder.py:62-97) -- env_runners/episode_return_mean / _min / _max, episode_len_mean,
+ * agent_episode_returns_mean/<agent>, module_episode_returns_mean/shared_policy over the last
+ * metrics_num_episodes_for_smoothing (100) episodes, and num_env_steps_sampled, num_agent_steps_sampled/<agent>.
+ * Here the window is a ring of `window` slots in device memory and the open episodes' sums sit beside it, advanced by
+ * one small kernel after each step, with no host synchronisation.  MARL handles with marl_wrapper = 1 only
+ * (CH_ERR_UNSUPPORTED otherwise).  All arrays are caller-owned device memory; N = the handle's num_drones.
+ * (RLlib is not installed here: restated from its source, "parity unpinned".)
+ * The episode rule is ch_marl_eval_record's (marl_wrapper.py:77-119): an agent adds (double)reward and one step only
+ * where it was live at the start of the step (the reward of an agent that is not live is never read); an env's
+ * episode ends where reset_happened[e] is set; a truncation ends nothing. */
+typedef struct ch_marl_ep_ring {
+    int32_t  window;        /* W >= 1: RLlib's metrics_num_episodes_for_smoothing (100) */
+    int32_t  _pad;
+    double*  ep_return;     /* device [W]: the sum over the agents, in agent order, of agent_return */
+    double*  agent_return;  /* device [W][N] */
+    int32_t* ep_length;     /* device [W]: env steps of the episode */
+    int32_t* agent_length;  /* device [W][N]: the steps the agent was live in */
+    int32_t* ep_env;        /* device [W]: the env it came from */
+    int64_t* total;         /* device [1]: episodes appended since begin; episode k lives in slot k % W */
+    double*  acc_return;    /* device [E][N]: the open episodes' running state */
+    int32_t* acc_length;    /* device [E][N] */
+    int32_t* acc_steps;     /* device [E] */
+    int64_t* env_steps;     /* device [1]: env steps recorded since begin (E per recorded step) */
+    int64_t* agent_steps;   /* device [N]: live agent-steps since begin, per agent index */
+} ch_marl_ep_ring;
+
+/* total, the counters and the accumulators = 0 (the slots are not cleared: the ring holds episodes
+ * max(0, total - W) .. total - 1).  An episode that is open at begin counts from zero. */
+int ch_marl_ep_ring_begin(ch_handle* h, const ch_marl_ep_ring* ring, void* stream);
+
+/* After a ch_step with CH_STEP_AUTORESET on the same stream.  live: device uint8 [E][N], the agents live at the start
+ * of that step (ch_marl_eval_mark's, or a rollout buffer's agent_mask[t]).  io->reward and io->reset_happened are
+ * required (CH_ERR_INVALID otherwise; nothing else of the io is read).  Every env's live agents add their rewards to
+ * the accumulators; then the C envs with reset_happened[e] != 0 are appended in ascending env order -- rank r among
+ * them is episode total + r and goes to slot (total + r) % W; when C > W only the last W of the step (r >= C - W)
+ * are written, so that every slot has one writer -- their accumulators go back to 0, and total += C.  Two launches:
+ * one thread per env accumulates (the live agent-steps, a pure count, with one integer atomic per wave and agent, as
+ * ch_marl_eval_record counts `remaining`); then one workgroup counts the ended envs and (C > 0) ranks them (wave
+ * ballots and a scan of the wave totals) over the envs in chunks of 1024.  Plain stores, no atomic on a float, every
+ * float64 sum by one thread in agent order: the same inputs give the same bits. */
+int ch_marl_ep_ring_record(ch_handle* h, const ch_marl_ep_ring* ring, const uint8_t* live, const ch_step_io* io,
+                           void* stream);
+
+/* ch_marl_rollout_collect with the episode ring: with ring != NULL, ch_marl_ep_ring_record runs once per step, right
+ * after step t's ch_step, with live = rb->agent_mask[t] (written by step t's store kernel, before the step) and the
+ * step's own reward / reset_happened, which nothing overwrites before step t + 1's ch_step: the forwards write the
+ * scratch outputs, and the store kernel of step t + 1, which posts step t, writes the buffer only.
+ * io->step->reset_happened is then required (CH_ERR_INVALID).  ring == NULL is ch_marl_rollout_collect exactly.  The
+ * rollout buffer's contents and the env state do not depend on the ring.  The call does not begin the ring: one ring
+ * spans the collections of a training run, and episodes span collection boundaries.  No host synchronisation. */
+int ch_marl_rollout_collect_log(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io,
+                                const ch_mlp* policy, const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda,
+                                const ch_marl_ep_ring* ring, void* stream);
+
 /* ---- On-device policy evaluation ---------------------------------------------------------
  * Replaces: stable_baselines3 evaluate_policy(model, env, n_eval_episodes, deterministic=True), as the CTDE driver
  * runs it after training and EvalCallback runs it during training (CTDECattleHerder.py:139-148, 185): every env
@@ -719,7 +775,9 @@ typedef struct ch_marl_ppo_data {
 int64_t ch_marl_ppo_param_count(const ch_marl_ppo_net* net);
 
 /* Host only.  No reference counterpart (torch autograd keeps its own buffers): floats of device scratch the calls
- * below need for minibatches of up to batch_size rows; -1 for an unsupported net or batch_size < 1. */
+ * below need for minibatches of up to batch_size rows; -1 for an unsupported net or batch_size < 1.  The size covers
+ * ch_marl_ppo_train_log as well: it includes that call's region of 33 floats per 16-row tile (a tile's sum, and each
+ * row's value and target), whichever call the scratch is for. */
 int64_t ch_marl_ppo_scratch_size(const ch_marl_ppo_net* net, int64_t batch_size);
 
 /* Replaces: the learner's compute_losses + backward for one minibatch.  idx: int64 [batch], rows of `data`;
@@ -742,6 +800,27 @@ int ch_marl_ppo_adam(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, 
 int ch_marl_ppo_train(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
                       const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                       float* stats, float* scratch, void* stream);
+
+/* ch_marl_ppo_train with the rest of RLlib's learner record (learners/shared_policy/...) per minibatch step.  stats is
+ * required: [steps][CH_MARL_PPO_LOG_STATS], columns 0-4 what ch_marl_ppo_train writes into [steps][5] from the same
+ * state, then
+ *   vf_loss_unclipped  = mean((v - target)^2) before the clamp (float32: the loss's own squared errors, summed per
+ *                        16-row tile in row order and over the tiles in index order),
+ *   total_loss         = policy_loss + vf_loss_coeff * vf_loss - entropy_coeff * entropy + kl_coeff * kl, the sum
+ *                        formed in float64 from columns 0-3 and the coefficient on the device, rounded once,
+ *   vf_explained_var   = RLlib's explained_variance(value_targets, values) over the minibatch:
+ *                        max(-1, 1 - var(y - v) / (var(y) + 1e-6)) with torch's unbiased variances; NaN for a one-row
+ *                        minibatch (0 / 0), and a NaN stays a NaN under the max.
+ * DIFFERENCE: RLlib computes the variances in float32; the differences cancel, so here both are two-pass float64
+ * reductions (the means, then the squared deviations) over the exactly widened float32 y and v -- the v the loss
+ * used -- in a fixed order (thread t of one workgroup adds rows t, t + 256, ..., a fixed tree adds the threads), and
+ * the result is rounded once.  (Restated from RLlib's source: parity unpinned.)
+ * The weights, m, v, the step count and columns 0-4 are what ch_marl_ppo_train leaves, bit for bit.  The forward-
+ * backward and Adam kernels are instantiations of their own: ch_marl_ppo_train launches what it launched before. */
+#define CH_MARL_PPO_LOG_STATS 8   /* policy loss, vf loss, entropy, kl, grad norm, vf_loss_unclipped, total_loss, vf_explained_var */
+int ch_marl_ppo_train_log(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
+                          const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
+                          float* stats, float* scratch, void* stream);
 
 /* ---- Device-side evaluator log: the per-step rows of update_evaluation_metrics ---------------------------------
  * Replaces: the reference's logging while is_evaluating is set -- BaseAviary.update_evaluation_metrics (sb3_envs/

@@ -12,8 +12,8 @@ CSRC = os.path.join(ROOT, "csrc")
 BUILD = os.path.join(ROOT, "build")
 LIB = os.path.join(PKG, "libcattleherd.so")
 SOURCES = ["ch_kernels.hip", "ch_step.hip", "ch_step_multi.hip", "ch_policy.hip", "ch_aux.hip", "ch_ppo.hip", "ch_eval.hip",
-           "ch_marl_eval.hip", "ch_eval_log.hip", "ch_ep_ring.hip", "ch_api.cpp", "ch_api_policy.cpp", "ch_api_ppo.cpp", "ch_api_eval.cpp",
-           "ch_api_marl_eval.cpp", "ch_api_eval_log.cpp", "ch_api_train_log.cpp", "ch_mlp_plan.cpp"]
+           "ch_marl_eval.hip", "ch_eval_log.hip", "ch_ep_ring.hip", "ch_marl_ep_ring.hip", "ch_api.cpp", "ch_api_policy.cpp", "ch_api_ppo.cpp", "ch_api_eval.cpp",
+           "ch_api_marl_eval.cpp", "ch_api_eval_log.cpp", "ch_api_train_log.cpp", "ch_api_marl_train_log.cpp", "ch_mlp_plan.cpp"]
 # per-source flags: ch_step_multi.hip's step loop keeps k_step2's register allocation only with machine LICM off
 # (ch_step_multi.hip header)
 SOURCE_FLAGS = {"ch_step_multi.hip": ["-mllvm", "-disable-machine-licm"]}

@@ -31,7 +31,8 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark", "ch_marl_eval_record",
            "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark", "ch_eval_log_record", "ch_eval_log_run",
            "ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
-           "ch_explained_variance_scratch", "ch_explained_variance")
+           "ch_explained_variance_scratch", "ch_explained_variance", "ch_marl_ep_ring_begin", "ch_marl_ep_ring_record",
+           "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
@@ -39,6 +40,11 @@ _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_ma
 # the SB3 training log's symbols (cattleherd/train_log.py): an older library lacks them too
 _TRAIN_LOG_EXPORTS = ("ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
                       "ch_explained_variance_scratch", "ch_explained_variance")
+# the RLlib training log's (cattleherd/train_log.py, the MARL half): likewise
+_MARL_TRAIN_LOG_EXPORTS = ("ch_marl_ep_ring_begin", "ch_marl_ep_ring_record", "ch_marl_rollout_collect_log",
+                           "ch_marl_ppo_train_log")
+# ch_marl_ppo_train_log's columns: ch_marl_ppo_train's five, then vf_loss_unclipped, total_loss, vf_explained_var
+CH_MARL_PPO_LOG_STATS = 8
 CH_PPO_LOG_STATS = 6   # ch_ppo_train_log's columns: policy loss, value loss, mean entropy, grad norm, approx_kl, clip_fraction
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
@@ -154,6 +160,15 @@ class ChEpRing(ctypes.Structure):
         [(k, ctypes.c_void_p) for k in ("ep_return", "ep_length", "ep_env", "total")]
 
 
+# the RLlib training log's episode ring (ch_marl_ep_ring_*; cattleherd/train_log.py)
+MARL_RING_ARRAYS = ("ep_return", "agent_return", "ep_length", "agent_length", "ep_env", "total", "acc_return",
+                    "acc_length", "acc_steps", "env_steps", "agent_steps")
+
+
+class ChMarlEpRing(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_int32), ("_pad", ctypes.c_int32)] + [(k, ctypes.c_void_p) for k in MARL_RING_ARRAYS]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -239,8 +254,13 @@ def lib():
         L.ch_ppo_train_log.argtypes = L.ch_ppo_train.argtypes
         L.ch_explained_variance_scratch.argtypes = [i64]
         L.ch_explained_variance.argtypes = [vp, vp, i64, vp, vp, vp]
+    if hasattr(L, "ch_marl_ep_ring_record"):
+        L.ch_marl_ep_ring_begin.argtypes = [vp, P(ChMarlEpRing), vp]
+        L.ch_marl_ep_ring_record.argtypes = [vp, P(ChMarlEpRing), vp, P(ChStepIO), vp]
+        L.ch_marl_ppo_train_log.argtypes = L.ch_marl_ppo_train.argtypes
+    optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS
     for name in EXPORTS:
-        if name not in ("ch_last_error",) and (name not in ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS or hasattr(L, name)):
+        if name not in ("ch_last_error",) and (name not in optional or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int
     L.ch_mlp_packed_size.restype = ctypes.c_int64
     L.ch_ppo_param_count.restype = L.ch_ppo_scratch_size.restype = ctypes.c_int64

@@ -69,8 +69,9 @@ class NativeState:
         """``n_epochs`` calls of the flavour's ``*_train`` on the current stream of the model's device, each over the
         ``n`` row indices (int64, on the device) that ``draw()`` returns, in minibatches of ``batch_size``.  ``hp`` and
         ``data`` are the flavour's hparams and data structs; ``stats``: None or the per-step statistics' float32
-        tensor ``[n_epochs * steps per epoch, k]``.  ``log`` (SB3 flavour): ``*_train_log``, whose ``stats`` are
-        required and ``CH_PPO_LOG_STATS`` wide.  Returns the number of minibatch steps."""
+        tensor ``[n_epochs * steps per epoch, k]``.  ``log``: ``*_train_log``, whose ``stats`` are required and
+        ``CH_PPO_LOG_STATS`` (SB3 flavour) / ``CH_MARL_PPO_LOG_STATS`` (RLlib flavour) wide.  Returns the number of
+        minibatch steps."""
         import torch
         lib, dev = _lib.lib(), self.model.device
         net = net_struct(self.fl, self.model)   # the parameters' storage as it is now (a .to() or .data = ... moves it)

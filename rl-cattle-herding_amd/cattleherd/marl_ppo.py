@@ -16,6 +16,10 @@ epoch's last minibatch is partial, where RLlib's cyclic iterator wraps around to
 ``backend="torch"`` (the default, eager autograd) is the reference; ``backend="native"`` (or
 ``CH_PPO_BACKEND=native``) runs the same minibatch sequence through ``ch_marl_ppo_train`` (csrc/ch_ppo.hip compiled
 for this loss and head): three hand-written launches per step on the parameters' own storage.
+
+``log_stats=True`` makes ``train`` also fill ``last_log`` with RLlib's ``learners/shared_policy`` logger keys, from
+device-side data read once at the end (native: ``ch_marl_ppo_train_log``); ``train_log.rllib_result`` joins it with a
+``MarlEpisodeRing``'s env-runner keys.
 """
 import math
 import os
@@ -130,6 +134,22 @@ def marl_ppo_net(model):
 
 
 STATS = ("policy_loss", "vf_loss", "entropy", "kl", "grad_norm")
+# with log_stats: ch_marl_ppo_train_log's columns
+LOG_STATS = STATS + ("vf_loss_unclipped", "total_loss", "vf_explained_var")
+# RLlib's learners/shared_policy/* keys that ``last_log`` holds
+LOG_KEYS = ("policy_loss", "vf_loss", "vf_loss_unclipped", "vf_explained_var", "entropy", "mean_kl_loss", "total_loss",
+            "curr_kl_coeff", "curr_entropy_coeff", "gradients_default_optimizer_global_norm", "num_module_steps_trained")
+
+
+def explained_variance(y, pred):
+    """RLlib's ``explained_variance(y, pred)``: ``max(-1, 1 - var(y - pred) / (var(y) + 1e-6))`` with torch's unbiased
+    variances, in the tensors' dtype; NaN for one element (0 / 0), which the max keeps."""
+    torch = _torch()
+
+    def var(x):
+        d = x - x.mean()
+        return (d * d).sum() / (x.numel() - 1)
+    return torch.maximum(torch.full_like(y[:1].sum(), -1.0), 1.0 - var(y - pred) / (var(y) + 1e-6))
 
 
 class MarlPPOUpdate:
@@ -137,11 +157,16 @@ class MarlPPOUpdate:
     untouched).  ``backend``: ``"torch"`` (eager autograd) or ``"native"`` (``ch_marl_ppo_train``); ``None`` reads
     ``CH_PPO_BACKEND`` (default ``"torch"``).  ``kl_coeff`` is a one-float device tensor, adapted after each
     ``train``; ``stats`` holds the last ``train``'s per-step ``[steps, 5]`` statistics (``STATS``) on the device.
-    RLlib is not installed: restated from its source, parity unpinned."""
+    ``log_stats=True`` (both backends; native: ``ch_marl_ppo_train_log``): ``stats`` is ``[steps, 8]`` (``LOG_STATS``:
+    also the unclipped value loss, the total loss and RLlib's ``vf_explained_var`` of each minibatch -- the torch
+    backend computes them in the model's dtype, the native one as include/cattleherd.h states), and ``train`` fills
+    ``last_log`` with RLlib's ``learners/shared_policy`` keys (``LOG_KEYS``), each the last minibatch's value -- the
+    one the KL rule uses -- read with one small copy.  RLlib is not installed: restated from its source, parity
+    unpinned."""
 
     def __init__(self, model, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, clip_param=0.3, vf_clip_param=10.0,
                  vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2, kl_target=0.01, num_epochs=30,
-                 minibatch_size=128, grad_clip=None, log_std_clip=20.0, seed=0, backend=None):
+                 minibatch_size=128, grad_clip=None, log_std_clip=20.0, seed=0, backend=None, log_stats=False):
         torch = _torch()
         if backend is None:
             backend = os.environ.get("CH_PPO_BACKEND", "torch")
@@ -164,10 +189,12 @@ class MarlPPOUpdate:
         self.gen = torch.Generator(device=model.device).manual_seed(seed)
         self.stats = None
         self.sgd_steps = 0
+        self.log_stats, self.last_log = bool(log_stats), {}
 
     # ---- the loss (the reference: tests compare the native kernels with this in float64) -------------------------
     def _loss(self, obs, actions, old_log_prob, old_dist, advantages, value_targets):
-        """(total loss, [policy loss, value loss, mean entropy, mean KL]) of one minibatch, in the model's dtype."""
+        """(total loss, [policy loss, value loss, mean entropy, mean KL]) of one minibatch, in the model's dtype; with
+        ``log_stats`` the statistics go on with [unclipped value loss, total loss, vf_explained_var]."""
         torch = _torch()
         A = self.model.act_dim
         dist = self.model.dist_inputs(obs, self.log_std_clip)
@@ -180,10 +207,15 @@ class MarlPPOUpdate:
                          advantages * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param))
         entropy = (log_std + 0.5 + 0.5 * math.log(2.0 * math.pi)).sum(-1)
         kl = (log_std - log_std_p + (torch.exp(2.0 * log_std_p) + (mean_p - mean) ** 2) / (2.0 * var) - 0.5).sum(-1)
-        vf = torch.clamp((self.model.values(obs) - value_targets) ** 2, 0.0, self.vf_clip_param)
+        values = self.model.values(obs)
+        vf_unclipped = (values - value_targets) ** 2
+        vf = torch.clamp(vf_unclipped, 0.0, self.vf_clip_param)
         total = torch.mean(-surr + self.vf_loss_coeff * vf - self.entropy_coeff * entropy) + \
             self.kl_coeff.to(kl.dtype)[0] * torch.mean(kl)
-        return total, torch.stack([-surr.mean(), vf.mean(), entropy.mean(), kl.mean()]).detach()
+        stats = [-surr.mean(), vf.mean(), entropy.mean(), kl.mean()]
+        if self.log_stats:
+            stats += [vf_unclipped.mean(), total, explained_variance(value_targets, values)]
+        return total, torch.stack(stats).detach()
 
     def _sgd(self, data, idx, stats_row):
         """One minibatch step in torch: gather, loss, backward, the optional global-norm clip, Adam."""
@@ -197,8 +229,9 @@ class MarlPPOUpdate:
         else:
             norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in params]))
         self.opt.step()
-        stats_row[:4] = st
+        stats_row[:4] = st[:4]
         stats_row[4] = norm
+        stats_row[5:] = st[4:]
 
     # ---- one training iteration -----------------------------------------------------------------------------------
     def _prepare(self, rb):
@@ -237,7 +270,8 @@ class MarlPPOUpdate:
         n, bs = live.numel(), self.minibatch_size
         nb = (n + bs - 1) // bs
         steps = self.num_epochs * nb
-        self.stats = torch.zeros((steps, 5), dtype=data[0].dtype, device=self.model.device)
+        self.stats = torch.zeros((steps, len(LOG_STATS if self.log_stats else STATS)), dtype=data[0].dtype,
+                                 device=self.model.device)
         if self.backend == "native":
             self._train_native(data, live, n)
         else:
@@ -249,7 +283,30 @@ class MarlPPOUpdate:
                     k += 1
         self._adapt_kl(self.stats[-1, 3].to(torch.float32))
         self.sgd_steps += steps
+        if self.log_stats:
+            self._fill_log(n)
         return steps
+
+    def _fill_log(self, n):
+        """RLlib's learner record of the call: the last minibatch's statistics and the adapted coefficient, gathered
+        on the device and read once.  ``n``: the live rows; every epoch passes over each once (the last minibatch is
+        partial), so the module trained on ``n * num_epochs`` rows."""
+        torch = _torch()
+        host = torch.cat([self.stats[-1].double(), self.kl_coeff.double()]).cpu().numpy()      # the one read
+        st = dict(zip(LOG_STATS, host))
+        self.last_log = {
+            "policy_loss": float(st["policy_loss"]),
+            "vf_loss": float(st["vf_loss"]),
+            "vf_loss_unclipped": float(st["vf_loss_unclipped"]),
+            "vf_explained_var": float(st["vf_explained_var"]),
+            "entropy": float(st["entropy"]),
+            "mean_kl_loss": float(st["kl"]),
+            "total_loss": float(st["total_loss"]),
+            "curr_kl_coeff": float(host[-1]),
+            "curr_entropy_coeff": self.entropy_coeff,
+            "gradients_default_optimizer_global_norm": float(st["grad_norm"]),
+            "num_module_steps_trained": int(n) * self.num_epochs,
+        }
 
     def _train_native(self, data, live, n):
         """The same permutations as the torch path, one ch_marl_ppo_train call per epoch on the current stream."""
@@ -264,7 +321,7 @@ class MarlPPOUpdate:
                               self.grad_clip if self.grad_clip is not None else 0.0, self.kl_coeff.data_ptr())
         self._native.train(hp, ChMarlPpoData(*(t.data_ptr() for t in data), data[0].shape[0]), self.num_epochs, n,
                            self.minibatch_size, lambda: live[torch.randperm(n, device=dev, generator=self.gen)],
-                           self.stats)
+                           self.stats, log=self.log_stats)
 
     # Adam's moments over the flat parameters and its step count (native backend)
     exp_avg = property(lambda self: self._native.exp_avg)

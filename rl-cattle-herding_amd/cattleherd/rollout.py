@@ -200,12 +200,19 @@ class DeviceMarlRolloutBuffer:
                                                 ctypes.POINTER(L.ChMlp), ctypes.POINTER(L.ChMlp), ctypes.c_uint64,
                                                 ctypes.c_float, ctypes.c_float, vp]
         lib.ch_marl_rollout_collect.restype = ctypes.c_int
+        if hasattr(lib, "ch_marl_rollout_collect_log"):   # (an older library, e.g. an A/B baseline, lacks it)
+            lib.ch_marl_rollout_collect_log.argtypes = lib.ch_marl_rollout_collect.argtypes[:-1] + \
+                [ctypes.POINTER(L.ChMarlEpRing), vp]
+            lib.ch_marl_rollout_collect_log.restype = ctypes.c_int
         self._lib = lib
 
-    def collect(self, policy, value, seed=0):
+    def collect(self, policy, value, seed=0, ring=None):
         """RLlib PPO sampling for n_steps steps of every env and agent, on the device, in one native call.
         ``policy``: DevicePolicy 86 -> ... -> 2 * act_dim (mean, log_std: RLlib's DiagGaussian inputs), ``value``:
-        DevicePolicy 86 -> ... -> 1 (RLlib PPO's separate value branch, vf_share_layers=False)."""
+        DevicePolicy 86 -> ... -> 1 (RLlib PPO's separate value branch, vf_share_layers=False).
+        ``ring``: a ``train_log.MarlEpisodeRing`` of this batch; every step is recorded in it -- the live agents'
+        rewards, and the ended episodes in env order (ch_marl_rollout_collect_log: two small launches more per step; the
+        buffer's contents and the env state do not depend on it).  The ring is not begun here: it spans collections."""
         b = self.batch
         for net in (policy, value):
             net._ensure_packed()
@@ -213,7 +220,12 @@ class DeviceMarlRolloutBuffer:
         io.step = ctypes.pointer(b._io)
         io.policy_out, io.value_out, io.env_actions = (self.policy_out.data_ptr(), self.value_out.data_ptr(),
                                                        self.env_actions.data_ptr())
-        L.check(self._lib.ch_marl_rollout_collect(b.handle, ctypes.byref(self._rb), ctypes.byref(io),
-                                                  ctypes.byref(policy._net), ctypes.byref(value._net), int(seed),
-                                                  self.gamma, self.gae_lambda, b._stream()), b.handle)
+        args = (b.handle, ctypes.byref(self._rb), ctypes.byref(io), ctypes.byref(policy._net), ctypes.byref(value._net),
+                int(seed), self.gamma, self.gae_lambda)
+        if ring is None:
+            L.check(self._lib.ch_marl_rollout_collect(*args, b._stream()), b.handle)
+            return self
+        if ring.batch is not b:
+            raise ValueError("the episode ring belongs to another batch")
+        L.check(self._lib.ch_marl_rollout_collect_log(*args, ctypes.byref(ring._ring), b._stream()), b.handle)
         return self

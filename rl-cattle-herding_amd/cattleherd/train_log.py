@@ -11,6 +11,12 @@ over ``ch_ppo_train_log`` and ``explained_variance`` below.
 Semantics restated from SB3 2.x; SB3 is not installed here, so the restatement is "parity unpinned" to its source.
 One difference is deliberate: SB3's ``explained_variance`` is float32 numpy, here the float32 inputs are widened
 exactly and every sum is float64 (two passes: the means, then the squared deviations).  CTDE batches only.
+
+The DTDE (MARL) driver is watched through RLlib's result dict instead: ``MarlEpisodeRing`` is the env runners' window
+of the last ``metrics_num_episodes_for_smoothing`` episodes with per-agent returns, and their sampling counters, as
+device arrays (``ch_marl_ep_ring``; inside the native collection with ``DeviceMarlRolloutBuffer.collect(...,
+ring=ring)``); ``MarlPPOUpdate(..., log_stats=True)`` (cattleherd/marl_ppo.py) holds the learner's keys, and
+``rllib_result`` nests the two as RLlib does.  RLlib is not installed either: restated, "parity unpinned".
 """
 import ctypes
 
@@ -103,3 +109,149 @@ def explained_variance(values, returns, out=None):
         L.check(lib.ch_explained_variance(values.data_ptr(), returns.data_ptr(), n, out.data_ptr(), scratch.data_ptr(),
                                           torch.cuda.current_stream(dev).cuda_stream))
     return out
+
+
+# ---- the DTDE (MARL) driver: RLlib's result dict ----------------------------------------------------------------
+POLICY_ID = "shared_policy"   # DTDECattleHerder.py: policies = {"shared_policy"}, every agent mapped to it
+
+
+def marl_summary_of(entries, num_episodes, env_steps, agent_steps):
+    """RLlib's env-runner keys of a window of episodes.  ``entries``: ``(return, length, agent_returns [N],
+    agent_lengths [N], env)`` per episode, oldest first; ``num_episodes``: the episodes since the previous report;
+    ``env_steps`` / ``agent_steps [N]``: the sampling counters.  ``episode_return_mean`` / ``_min`` / ``_max`` and
+    ``episode_len_mean`` / ``_min`` / ``_max`` over the window; ``agent_episode_returns_mean/agent_i``: the mean of
+    agent i's return over the window's episodes it took part in (``agent_length > 0``; an agent of no episode has no
+    key: ``marl_eval.episode_metrics``' rule and ids); ``module_episode_returns_mean/shared_policy``: every agent acts
+    through the one module, so its return of an episode is the episode's.  An empty window has no episode keys."""
+    out = {}
+    if entries:
+        ret = np.array([e[0] for e in entries], np.float64)
+        length = np.array([e[1] for e in entries], np.int64)
+        a_ret = np.array([e[2] for e in entries], np.float64).reshape(len(entries), -1)
+        a_len = np.array([e[3] for e in entries], np.int64).reshape(len(entries), -1)
+        out.update({"episode_return_mean": float(ret.mean()), "episode_return_min": float(ret.min()),
+                    "episode_return_max": float(ret.max()), "episode_len_mean": float(length.mean()),
+                    "episode_len_min": int(length.min()), "episode_len_max": int(length.max())})
+        for i in range(a_ret.shape[1]):
+            took_part = a_len[:, i] > 0
+            if took_part.any():
+                out[f"agent_episode_returns_mean/agent_{i}"] = float(a_ret[took_part, i].mean())
+        out[f"module_episode_returns_mean/{POLICY_ID}"] = float(ret.mean())
+    out["num_episodes"] = int(num_episodes)
+    out["num_env_steps_sampled"] = int(env_steps)
+    for i, n in enumerate(agent_steps):
+        out[f"num_agent_steps_sampled/agent_{i}"] = int(n)
+    return out
+
+
+class MarlEpisodeRing:
+    """The env runners' episode window of a MARL ``HerdBatch`` as device arrays (``ch_marl_ep_ring``; N =
+    ``batch.num_drones``): ``ep_return`` float64 [W], ``agent_return`` float64 [W, N], ``ep_length`` / ``ep_env``
+    int32 [W], ``agent_length`` int32 [W, N], ``total`` int64 [1] (episodes appended since ``begin``; episode k lives
+    in slot ``k % W``), the counters ``env_steps`` int64 [1] and ``agent_steps`` int64 [N], and the open episodes'
+    running state ``acc_return`` float64 [E, N], ``acc_length`` int32 [E, N], ``acc_steps`` int32 [E].  All are views
+    of one device buffer, the window and the counters at its head, so ``entries()`` and ``summary()`` are one copy."""
+
+    HEAD = ("ep_return", "agent_return", "total", "env_steps", "agent_steps", "ep_length", "agent_length", "ep_env")
+    ARRAYS = HEAD + ("acc_return", "acc_length", "acc_steps")
+
+    def __init__(self, batch, window=100):
+        if batch.mode != L.CH_MODE_MARL:
+            raise ValueError("the per-agent episode ring is for MARL batches")
+        self.batch, self.window = batch, int(window)
+        if self.window < 1:
+            raise ValueError("window must be >= 1")
+        torch = batch.torch
+        W, E, N = self.window, batch.n_envs, batch.num_drones
+        f64, i64, i32 = (torch.float64, np.float64, 8), (torch.int64, np.int64, 8), (torch.int32, np.int32, 4)
+        shapes = {"ep_return": (f64, (W,)), "agent_return": (f64, (W, N)), "total": (i64, (1,)),
+                  "env_steps": (i64, (1,)), "agent_steps": (i64, (N,)), "ep_length": (i32, (W,)),
+                  "agent_length": (i32, (W, N)), "ep_env": (i32, (W,)), "acc_return": (f64, (E, N)),
+                  "acc_length": (i32, (E, N)), "acc_steps": (i32, (E,))}
+        # the 8-byte arrays of each part come first, and the head is padded to 8 bytes: every view is aligned
+        at, off = {}, 0   # name -> (byte offset, bytes, torch dtype, numpy dtype, shape): the one table every view uses
+        for k in self.ARRAYS:
+            if k == "acc_return":
+                off = self._head = (off + 7) // 8 * 8
+            (dt, np_dt, size), shape = shapes[k]
+            at[k] = (off, int(np.prod(shape)) * size, dt, np_dt, shape)
+            off += at[k][1]
+        self._buf = torch.zeros(off, dtype=torch.uint8, device=batch.device)
+        self._at = at
+        ring = L.ChMarlEpRing()
+        ring.window = W
+        for k, (o, n, dt, _, shape) in at.items():
+            setattr(self, k, self._buf[o:o + n].view(dt).view(shape))
+            setattr(ring, k, getattr(self, k).data_ptr())
+        self._ring = ring
+        self._reported = 0   # `total` at the previous summary()
+
+    def begin(self):
+        """Empty the ring (ch_marl_ep_ring_begin): ``total``, the counters and the open episodes' sums to zero -- an
+        episode that is open now counts from zero."""
+        b = self.batch
+        L.check(L.lib().ch_marl_ep_ring_begin(b.handle, ctypes.byref(self._ring), b._stream()), b.handle)
+        self._reported = 0
+        return self
+
+    def record(self, live, io=None):
+        """After a step: the rewards of the agents that were live at its start (``live``: uint8 [E, N] device tensor)
+        into the open episodes' sums, and the episodes that ended in it into the ring, in env order
+        (ch_marl_ep_ring_record on the batch's step outputs, or on another ``ChStepIO``)."""
+        b = self.batch
+        torch = b.torch
+        if live.dtype != torch.uint8 or not live.is_contiguous() or live.numel() != b.n_envs * b.num_drones or \
+                live.device != self._buf.device:
+            raise ValueError("live must be a contiguous uint8 [n_envs, num_drones] tensor on the batch's device")
+        L.check(L.lib().ch_marl_ep_ring_record(b.handle, ctypes.byref(self._ring), live.data_ptr(),
+                                               b._io_ref if io is None else ctypes.byref(io), b._stream()), b.handle)
+
+    def _views(self, raw):
+        out = {}
+        for k, (o, n, _, np_dt, shape) in self._at.items():
+            if o + n > len(raw):   # (a copy of the head alone)
+                break
+            out[k] = raw[o:o + n].view(np_dt).reshape(shape)
+        return out
+
+    def arrays(self):
+        """Every array as numpy (one copy of the whole buffer; synchronises)."""
+        return self._views(self._buf.cpu().numpy())
+
+    def _head_arrays(self):
+        return self._views(self._buf[:self._head].cpu().numpy())   # the one copy
+
+    @staticmethod
+    def _entries(a, W):
+        total = int(a["total"][0])
+        return [(a["ep_return"][k % W], int(a["ep_length"][k % W]), a["agent_return"][k % W].copy(),
+                 a["agent_length"][k % W].astype(np.int64), int(a["ep_env"][k % W]))
+                for k in range(max(0, total - W), total)]
+
+    def entries(self):
+        """The window's content, oldest to newest: a list of ``(return, length, agent_returns [N], agent_lengths [N],
+        env)``.  One small device-to-host copy (synchronises)."""
+        return self._entries(self._head_arrays(), self.window)
+
+    def count(self):
+        """Episodes appended since ``begin`` (one 8-byte copy; synchronises)."""
+        return int(self.total.item())
+
+    def summary(self):
+        """RLlib's env-runner keys (``marl_summary_of``) from one copy of the window and the counters;
+        ``num_episodes`` counts the episodes appended since the previous ``summary()`` (or ``begin``)."""
+        a = self._head_arrays()
+        total = int(a["total"][0])
+        out = marl_summary_of(self._entries(a, self.window), total - self._reported, int(a["env_steps"][0]),
+                              a["agent_steps"].tolist())
+        self._reported = total
+        return out
+
+
+def rllib_result(ring, update):
+    """One training iteration's record as RLlib's result dict nests it: ``{"env_runners": ring.summary(), "learners":
+    {"shared_policy": update.last_log}}`` (a ``MarlEpisodeRing`` and a ``MarlPPOUpdate(log_stats=True)`` after
+    ``train``)."""
+    if not update.last_log:
+        raise ValueError("rllib_result: the update holds no record (MarlPPOUpdate(log_stats=True), after train())")
+    return {"env_runners": ring.summary(), "learners": {POLICY_ID: dict(update.last_log)}}

@@ -459,8 +459,10 @@ int ch_rollout_collect_log(ch_handle* h, const ch_rollout* rb, const ch_rollout_
     return rollout_collect(h, rb, io, actor, critic, log_std, seed, gamma, gae_lambda, bootstrap_truncated, ring, stream);
 }
 
-int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
-                            const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream) {
+// ch_marl_rollout_collect and ch_marl_rollout_collect_log (`ring`: NULL, or the episode ring every step is recorded in)
+static int marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
+                                const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda,
+                                const ch_marl_ep_ring* ring, void* stream) {
     if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_marl_rollout_collect: NULL handle");
     if (h->cfg.mode != CH_MODE_MARL)
         return fail(h, CH_ERR_UNSUPPORTED, "ch_marl_rollout_collect: the per-agent rollout is for MARL handles");
@@ -479,6 +481,8 @@ int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_ma
     if (policy->dims[policy->n_layers] != 2 * rb->act_dim || value->dims[value->n_layers] != 1)
         return fail(h, CH_ERR_INVALID, "ch_marl_rollout_collect: the policy must output 2 * act_dim (mean, log_std), the value net 1");
     int rc;
+    MarlRingArgs er;   // the recorder's arguments: the ring and this io's reward / reset_happened
+    if (ring && (rc = marl_ring_args(h, ring, sio, er, "ch_marl_rollout_collect_log"))) return rc;
     MlpArgs fp, fv;
     if ((rc = policy_args(h, policy, sio->obs, io->policy_out, fp, "ch_marl_rollout_collect (policy)"))) return rc;
     if ((rc = policy_args(h, value, sio->obs, io->value_out, fv, "ch_marl_rollout_collect (value)"))) return rc;
@@ -515,12 +519,31 @@ int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_ma
         HIP_TRY(h, launch_marl_rollout(a, 0, st));
         s.obs = (in_place && t + 1 < rb->n_steps) ? rb->obs + (size_t)(t + 1) * slot : sio->obs;
         if ((rc = ch_step(h, &s, stream))) return rc;
+        // The episode ring: step t's reward / reset_happened are written by the step above and by nothing else before
+        // step t + 1's ch_step -- the forwards write the scratch outputs, and the store kernel of step t + 1 (which
+        // posts step t: post_prev) and the GAE kernel read the step's outputs and write the buffer only.  agent_mask[t]
+        // was written by step t's store kernel, before the step.  So the recorder goes right here.
+        if (ring) {
+            er.live = rb->agent_mask + (size_t)t * a.rows;
+            HIP_TRY(h, launch_marl_ep_ring_record(er, st));
+        }
     }
     // V(obs after the last step) -> last_values, the last step's post, GAE
     fv.x = sio->obs;
     HIP_TRY(h, launch_mlp_multi(&fv, 1, st));
     HIP_TRY(h, launch_marl_rollout(a, 1, st));
     return CH_OK;
+}
+
+int ch_marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,
+                            const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda, void* stream) {
+    return marl_rollout_collect(h, rb, io, policy, value, seed, gamma, gae_lambda, nullptr, stream);
+}
+
+int ch_marl_rollout_collect_log(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io,
+                                const ch_mlp* policy, const ch_mlp* value, uint64_t seed, float gamma, float gae_lambda,
+                                const ch_marl_ep_ring* ring, void* stream) {
+    return marl_rollout_collect(h, rb, io, policy, value, seed, gamma, gae_lambda, ring, stream);
 }
 
 }  // extern "C"

@@ -211,7 +211,9 @@ int adam(const typename F::Net* net, const typename F::Hparams* hp, const float*
     return e == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
 }
 
-// log_stats (Sb3: ch_ppo_train_log): `stats` is required and CH_PPO_LOG_STATS wide, with approx_kl and clip_fraction
+// log_stats: `stats` is required and wider -- Sb3 (ch_ppo_train_log): CH_PPO_LOG_STATS, with approx_kl and
+// clip_fraction; Rllib (ch_marl_ppo_train_log): CH_MARL_PPO_LOG_STATS, with vf_loss_unclipped, total_loss and
+// vf_explained_var
 template <class F>
 int train(const typename F::Net* net, const typename F::Hparams* hp, const typename F::Data* data, const int64_t* idx,
           int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
@@ -232,7 +234,7 @@ int train(const typename F::Net* net, const typename F::Hparams* hp, const typen
     hipStream_t st = (hipStream_t)stream;
     float* grad = scratch + s.grad;
     long long* step = reinterpret_cast<long long*>(step_dev);
-    const int n_stats = log_stats ? CH_PPO_LOG_STATS : ppo_n_stats(F::kFlavour);
+    const int n_stats = !log_stats ? ppo_n_stats(F::kFlavour) : F::kFlavour == kPpoRllib ? CH_MARL_PPO_LOG_STATS : CH_PPO_LOG_STATS;
     int64_t k = 0;
     for (int64_t j = 0; j < n_idx; j += batch_size, ++k) {
         const int64_t batch = std::min(batch_size, n_idx - j);
@@ -294,6 +296,12 @@ int ch_marl_ppo_train(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp,
                       const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                       float* stats, float* scratch, void* stream) {
     return train<Rllib>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
+}
+
+int ch_marl_ppo_train_log(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
+                          const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
+                          float* stats, float* scratch, void* stream) {
+    return train<Rllib>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream, true);
 }
 
 }  // extern "C"

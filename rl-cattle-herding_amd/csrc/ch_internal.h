@@ -273,6 +273,25 @@ long long ev_scratch_doubles(long long n);   // n >= 1
 hipError_t launch_explained_variance(const float* values, const float* returns, long long n, double* out, double* scratch,
                                      hipStream_t st);
 
+// ch_marl_ep_ring.hip: the RLlib training log's episode ring for MARL handles (ch_marl_ep_ring_*): the ring, the open
+// episodes' accumulators, the sampling counters, and the outputs of the step the recorder follows
+struct MarlRingArgs {
+    long long E;
+    int N, W;                  // agents per env (<= kNMax), the ring's slots
+    double* ep_return;         // [W]
+    double* agent_return;      // [W][N]
+    int *ep_length, *agent_length, *ep_env;   // [W], [W][N], [W]
+    long long* total;          // [1]
+    double* acc_return;        // [E][N] the open episodes
+    int *acc_length, *acc_steps;              // [E][N], [E]
+    long long *env_steps, *agent_steps;       // [1], [N]
+    const uint8_t* live;       // [E][N] the agents live at the step's start
+    const float* reward;       // the step's reward [E][N]
+    const uint8_t* reset;      // the step's reset_happened [E]
+};
+hipError_t launch_marl_ep_ring_begin(const MarlRingArgs& a, hipStream_t st);
+hipError_t launch_marl_ep_ring_record(const MarlRingArgs& a, hipStream_t st);
+
 // ch_eval_log.hip: the device-side evaluator log (ch_eval_log_*): the table of include/cattleherd.h ch_eval_log, the
 // handle's state it reads, and the outputs of the step it follows
 struct EvalLogArgs {

@@ -68,7 +68,9 @@ struct PpoData {
 //             once) and |ratio - 1| > clip_range, behind the current minibatch's tiles (kPpoRllib: [tiles][4],
 //             with the sums of the rows' entropies and KL divergences)
 //   tile_dls  [tiles][act] log_std gradient partials (kPpoSb3)
-//   misc      [4]          mean entropy (kPpoSb3)
+//   misc      [4]          mean entropy (kPpoSb3); kPpoRllib keeps the training log's region here (written only with
+//             log_stats): [4] vf_loss_coeff, entropy_coeff, the KL coefficient; [tiles] the tiles' sums of unclipped
+//             squared value errors, then [bp][2] each row's (value, value target), behind the current minibatch's tiles
 //   partial   [workgroups] sum-of-squares partials of the gradient, one per workgroup that produced a piece of it
 //   grad      [n_params]   the flat gradient (ch_ppo_train)
 struct PpoScratch {
@@ -83,8 +85,10 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s);
 // ppo_launch_sumsq: the sum-of-squares partials of a given flat gradient (ch_ppo_adam), increments *step_dev.
 // ppo_launch_adam: every workgroup sums the partials in order, forms the clip coefficient and updates its slice;
 // workgroup 0 writes the step's statistics (ppo_n_stats of them) to `stats` when it is not NULL; log_stats (kPpoSb3):
-// CH_PPO_LOG_STATS of them, with approx_kl and clip_fraction (ch_ppo_train_log).  ppo_launch_stats: the statistics
-// alone (ch_ppo_grad, ch_marl_ppo_grad).
+// CH_PPO_LOG_STATS of them, with approx_kl and clip_fraction (ch_ppo_train_log).  log_stats with kPpoRllib
+// (ch_marl_ppo_train_log): both launches take the kPpoRllibLog kernels, which leave CH_MARL_PPO_LOG_STATS statistics,
+// with vf_loss_unclipped, total_loss and vf_explained_var.  ppo_launch_stats: the statistics alone (ch_ppo_grad,
+// ch_marl_ppo_grad).
 hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
                            float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
                            hipStream_t st, bool log_stats = false);

@@ -20,7 +20,9 @@
 // the KL penalty against the gathered old dist inputs and clips the value error, k_ppo_dw has no log_std workgroup and
 // k_ppo_adam a no-clip mode and five statistics.  kPpoSb3 is the step described above; for
 // ch_ppo_train_log a third k_ppo_fb instantiation (kFbSb3Log) also leaves per-tile sums of SB3's two diagnostics
-// (approx_kl, clip_fraction), which k_ppo_adam turns into two more statistics.
+// (approx_kl, clip_fraction), which k_ppo_adam turns into two more statistics.  For
+// ch_marl_ppo_train_log a fourth flavour (kPpoRllibLog) of k_ppo_fb and k_ppo_adam adds RLlib's vf_loss_unclipped,
+// total_loss and vf_explained_var.
 //
 // MFMA operand map (16x16x4 f32): lane l gives A[row l & 15][k slot l >> 4] and B[k slot l >> 4][col l & 15]; it
 // holds C/D[row 4 (l >> 4) + r][col l & 15] in register r.  Which k a slot stands for is free as long as A and B
@@ -149,13 +151,21 @@ struct FbArgs {
     const float* kl_coeff_dev;
 };
 
-// per-tile loss partials: the surrogate and the squared value error; kPpoRllib adds the entropy and the KL
-template <int F>
-constexpr int kStat = F == kPpoRllib ? 4 : 2;
-
 // k_ppo_fb's third flavour (ch_ppo_train_log): kPpoSb3 plus the per-tile sums of SB3's two diagnostics.  A kernel of
 // its own, so that ch_ppo_train's carries none of the float64 code.
 constexpr int kFbSb3Log = 2;
+// the fourth, of k_ppo_fb and of the Adam kernel (ch_marl_ppo_train_log): kPpoRllib plus what RLlib's learner record
+// lacks in the five statistics -- the critic workgroups leave the loss's coefficients, each tile's sum of unclipped
+// squared value errors and each row's (value, target) in the scratch region `misc` (unused by kPpoRllib otherwise:
+// [4] coefficients, [tiles] sums, [bp][2] rows), and k_ppo_adam turns them into vf_loss_unclipped, total_loss and
+// vf_explained_var.
+// Kernels of their own, so that ch_marl_ppo_train launches what it launched before.
+constexpr int kPpoRllibLog = 3;
+constexpr bool ppo_rllib(int F) { return F == kPpoRllib || F == kPpoRllibLog; }
+
+// per-tile loss partials: the surrogate and the squared value error; kPpoRllib adds the entropy and the KL
+template <int F>
+constexpr int kStat = ppo_rllib(F) ? 4 : 2;
 
 template <int F>
 __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
@@ -222,7 +232,7 @@ __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
 
     // the loss and its gradient with respect to the head's output, rows past the minibatch 0
     const int NO = net.dims[L];
-    if constexpr (F == kPpoRllib) {
+    if constexpr (ppo_rllib(F)) {
         if (ni == 0) {
             // 16 lanes per row.  The head is [mean (A), raw log_std (A)], log_std = the raw value clamped to +-ls_clip
             // (torch.clamp: the gradient passes inside the closed range).  Per row: the log-probability of the stored
@@ -273,6 +283,14 @@ __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
             const bool valid = row0 + tid < a.batch;
             const long long src = a.idx[min(row0 + tid, a.batch - 1)];
             const float err = os[tid * kLdo] - a.d.returns[src], e2 = err * err;
+            if constexpr (F == kPpoRllibLog) {
+                // the training log's share of the row: the squared error before the clamp (`tmp` is free in a critic
+                // workgroup), and the value and its target as the loss used them, for the explained variance
+                tmp[tid] = valid ? e2 : 0.0f;
+                float* vy = a.scratch + a.s.misc + 4 + a.s.tiles + 2 * (row0 + tid);
+                vy[0] = os[tid * kLdo];
+                vy[1] = a.d.returns[src];
+            }
             rowstat[tid] = valid ? fminf(e2, a.vf_clip) : 0.0f;
             os[tid * kLdo] = valid && e2 <= a.vf_clip ? a.vf_coef * 2.0f * err * inv_b : 0.0f;
         }
@@ -288,6 +306,16 @@ __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
                 }
                 a.scratch[a.s.tile_stat + 4 * tile + 2] = e;
                 a.scratch[a.s.tile_stat + 4 * tile + 3] = k;
+            }
+            if (F == kPpoRllibLog && ni == 1) {   // the tile's unclipped squared errors, rows in order
+                float u = 0.0f;
+                for (int r = 0; r < kPpoTile; ++r) u += tmp[r];
+                a.scratch[a.s.misc + 4 + tile] = u;
+                if (tile == 0) {   // and the loss's coefficients, as this kernel used them
+                    a.scratch[a.s.misc] = a.vf_coef;
+                    a.scratch[a.s.misc + 1] = a.ent_coef;
+                    a.scratch[a.s.misc + 2] = *a.kl_coeff_dev;
+                }
             }
         }
     } else {
@@ -565,6 +593,55 @@ struct AdamArgs {
                           // clip_fraction (ch_ppo_train_log)
 };
 
+// the workgroup's two sums in sy[0], sd[0]: a fixed tree over its 256 threads
+__device__ __forceinline__ void tree_sum2(double* sy, double* sd, double y, double d) {
+    const int t = threadIdx.x;
+    sy[t] = y; sd[t] = d;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) { sy[t] += sy[t + w]; sd[t] += sd[t + w]; }
+        __syncthreads();
+    }
+}
+
+// The three statistics ch_marl_ppo_train_log adds, by workgroup 0 (all of its threads get here) after stats4[0..4]:
+// vf_loss_unclipped from the tiles' sums in index order; total_loss as the reference's _loss forms it, in float64
+// from the four float32 means; vf_explained_var = max(-1, 1 - var(y - v) / (var(y) + 1e-6)) with unbiased variances
+// (RLlib's explained_variance(value_targets, values)).  The differences cancel, so both variances are two-pass float64
+// sums over the exactly widened float32 y and v, thread t adding rows t, t + 256, ... and a fixed tree the threads;
+// a one-row minibatch gives 0 / 0 = NaN, which the comparison below keeps (fmax would not).  Everything comes from the
+// scratch region `misc` as k_ppo_fb<kPpoRllibLog> left it: the loss's three coefficients, the tiles' sums, the rows.
+__device__ __forceinline__ void rllib_log_stats(const AdamArgs& a) {
+    __shared__ double sy[256], sd[256];
+    const int tid = threadIdx.x;
+    const float* log = a.misc + 4;
+    const float* vy = log + a.tiles;
+    double y = 0.0, d = 0.0;
+    for (long long i = tid; i < a.batch; i += 256) {
+        const double v = vy[2 * i], r = vy[2 * i + 1];
+        y += r; d += r - v;
+    }
+    tree_sum2(sy, sd, y, d);
+    const double my = sy[0] / (double)a.batch, md = sd[0] / (double)a.batch;
+    __syncthreads();
+    y = 0.0; d = 0.0;
+    for (long long i = tid; i < a.batch; i += 256) {
+        const double v = vy[2 * i], r = vy[2 * i + 1];
+        y += (r - my) * (r - my); d += (r - v - md) * (r - v - md);
+    }
+    tree_sum2(sy, sd, y, d);
+    if (tid != 0) return;
+    float u = 0.0f;
+    for (int t = 0; t < a.tiles; ++t) u += log[t];
+    a.stats4[5] = u / (float)a.batch;
+    a.stats4[6] = (float)((double)a.stats4[0] + (double)a.misc[0] * (double)a.stats4[1] -
+                          (double)a.misc[1] * (double)a.stats4[2] +
+                          (double)a.misc[2] * (double)a.stats4[3]);   // (thread 0 wrote the four just above)
+    const double n1 = (double)(a.batch - 1);
+    const double ev = 1.0 - (sd[0] / n1) / (sy[0] / n1 + 1e-6);
+    a.stats4[7] = (float)(ev < -1.0 ? -1.0 : ev);
+}
+
 template <int F>
 __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
     __shared__ float red[4];
@@ -579,14 +656,14 @@ __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
         for (int t = 0; t < a.tiles; ++t) {
             pl += a.tile_stat[kStat<F> * t];
             vl += a.tile_stat[kStat<F> * t + 1];
-            if constexpr (F == kPpoRllib) {
+            if constexpr (ppo_rllib(F)) {
                 en += a.tile_stat[4 * t + 2];
                 kl += a.tile_stat[4 * t + 3];
             }
         }
         a.stats4[0] = -pl / (float)a.batch;
         a.stats4[1] = vl / (float)a.batch;
-        if constexpr (F == kPpoRllib) {
+        if constexpr (ppo_rllib(F)) {
             a.stats4[2] = en / (float)a.batch;
             a.stats4[3] = kl / (float)a.batch;
             a.stats4[4] = norm;
@@ -604,13 +681,16 @@ __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
             }
         }
     }
+    if constexpr (F == kPpoRllibLog) {
+        if (blockIdx.x == 0 && (a.update & 2)) rllib_log_stats(a);   // (ch_marl_ppo_train_log: stats4 is required)
+    }
     if (!a.update) return;
     if (tid == 0) {
         // torch Adam's scalars in double, as its (non-capturable) step computes them on the host
         const double t = (double)*a.step_dev;
         const double bc1 = 1.0 - pow(a.beta1, t), bc2 = 1.0 - pow(a.beta2, t);
         sc[0] = (float)fmin(1.0, a.max_grad_norm / ((double)norm + 1e-6));   // clip_grad_norm_
-        if (F == kPpoRllib && !(a.max_grad_norm > 0.0)) sc[0] = 1.0f;        // grad_clip None
+        if (ppo_rllib(F) && !(a.max_grad_norm > 0.0)) sc[0] = 1.0f;     // grad_clip None
         sc[1] = (float)(a.lr / bc1);
         sc[2] = (float)(1.0 / sqrt(bc2));
     }
@@ -664,7 +744,7 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s) {
     }
     s.tile_stat = take(4LL * s.tiles);
     s.tile_dls = take(n.flavour == kPpoSb3 ? (long long)s.tiles * n.act_dim : 0);
-    s.misc = take(4);
+    s.misc = take(n.flavour == kPpoSb3 ? 4 : 4 + s.tiles + 2LL * s.bp);
     s.partial = take(std::max(dw_workgroups(n), kSumsqGrid));
     s.grad = take(n.n_params);
     s.total = o;
@@ -684,7 +764,8 @@ hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, c
     for (int ni = 0; ni < 2; ++ni)
         for (int li = 0; li < n.net[ni].layers; ++li) f.vec_w[ni][li] = n.net[ni].dims[li] % 4 == 0 && aligned16(n.net[ni].w[li]);
     const bool rllib = n.flavour == kPpoRllib;
-    hipLaunchKernelGGL(rllib ? k_ppo_fb<kPpoRllib> : log_stats ? k_ppo_fb<kFbSb3Log> : k_ppo_fb<kPpoSb3>,
+    hipLaunchKernelGGL(rllib ? (log_stats ? k_ppo_fb<kPpoRllibLog> : k_ppo_fb<kPpoRllib>)
+                             : (log_stats ? k_ppo_fb<kFbSb3Log> : k_ppo_fb<kPpoSb3>),
                        dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -748,9 +829,10 @@ hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, 
     adam_common(a, n, scratch, s, n_partials, batch, stats);
     a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
     a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
-    a.update = log_stats && n.flavour == kPpoSb3 ? 3 : 1;
+    a.update = log_stats ? 3 : 1;
     const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
-    hipLaunchKernelGGL(n.flavour == kPpoRllib ? k_ppo_adam<kPpoRllib> : k_ppo_adam<kPpoSb3>, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(n.flavour != kPpoRllib ? k_ppo_adam<kPpoSb3> : log_stats ? k_ppo_adam<kPpoRllibLog> : k_ppo_adam<kPpoRllib>,
+                       dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
