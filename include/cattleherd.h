@@ -123,6 +123,10 @@ int ch_shape(const ch_handle* h, int64_t* n_envs, int32_t* obs_rows, int32_t* ob
 /* Replaces: BaseAviary.reset (sb3_envs/BaseAviary.py:280-331; rllib_envs/BaseAviary.py:280-318).
  * Resets the envs whose mask byte is non-zero (mask = NULL: all) and writes their initial
  * observation into obs (device, [E][R][86]); other envs' obs rows are left untouched.
+ * A reset env's open episode is abandoned, as SB3's Monitor.reset drops its reward list: the running return and
+ * length behind ch_step_io.episode_stats start again from zero, and the abandoned steps are counted in neither
+ * CH_METRIC_EPISODES, CH_METRIC_RETURN_SUM nor CH_METRIC_LENGTH_SUM (CH_METRIC_STEPS and the other per-step sums keep
+ * them).  The call has no agent_active output: a reset env's live agents are the first NUM_DRONES (ch_get_state).
  * A full reset (mask = NULL) first reads and clears the handle's sticky device error word: it synchronises `stream`
  * (so it blocks the host and cannot be captured into a HIP graph), and a device error an earlier step recorded and no
  * ch_sync / ch_metrics / ch_get_state has reported yet is returned as CH_ERR_DEVICE after the reset has been done

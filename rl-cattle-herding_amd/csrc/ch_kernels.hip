@@ -568,6 +568,12 @@ __global__ __launch_bounds__(64) void k_env(StepParams<R> p) {
         __syncthreads();
     } else {
         do_reset = valid && (p.reset_mask == nullptr || p.reset_mask[e] != 0);
+        // an explicit reset abandons the open episode: its running return and length are dropped, uncounted
+        // (SB3 Monitor.reset clears its reward list); the step kernels zero these rows only where an episode ends
+        if (do_reset && t == 0) {
+            p.metrics[kMetricCurReturn * E + e] = 0;
+            p.metrics[kMetricCurLen * E + e] = 0;
+        }
     }
 
     // ---- auto-reset / reset ------------------------------------------------------------------

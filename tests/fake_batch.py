@@ -53,6 +53,7 @@ class FakeBatch:
         for e, env in enumerate(self.envs):
             if mask is None or bool(mask[e]):
                 self.obs[e] = torch.from_numpy(env.reset())
+                self._ret[e], self._len[e] = 0.0, 0.0   # the open episode is abandoned (ch_reset)
         return self.obs
 
     def step(self, actions=None, autoreset=True, random_actions=False, terminal_obs=True):

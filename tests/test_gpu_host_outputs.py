@@ -60,6 +60,36 @@ def test_outputs_to_host_equal_device_buffers(mode, E, n, m, level):
     b.close()
 
 
+@pytest.mark.parametrize("E", [1025, 2100])
+def test_outputs_to_host_compaction_beyond_one_chunk(E):
+    """More envs than one 1024-thread chunk of the ranked compaction (k_stage_ended): the slot base carried from
+    chunk to chunk and the partly filled last chunk (one env at E = 1025).  Env e reaches the time limit in step
+    1 + 7 e mod 40 where that is at most 20 (env 1024: step 9), so a few dozen envs end in every step on both sides
+    of env 1024; then every env ends in one step."""
+    from cattleherd.env import HerdBatch
+    b = HerdBatch(E, 2, 8, mode="ctde", curriculum_level=7, compat=False)
+    b.reset()
+    ends_at = 1 + (7 * np.arange(E)) % 40
+    # level 7: an env ends in the step it enters with its counter (4 per step) above the 80 s limit of 4800
+    b.set_state({"step_counter": np.where(ends_at <= 20, 4800 - 4 * (ends_at - 2), 0)})
+    host = b.host_outputs(ring=2, ended=True)
+    lo = hi = both = 0
+    for _ in range(20):
+        b.step(random_actions=True, autoreset=True, terminal_obs=True)
+        h = host.fetch()
+        assert _check_delivery(b, h) > 0
+        idx = h["ended_env"]
+        lo, hi = lo + int((idx < 1024).sum()), hi + int((idx >= 1024).sum())
+        both += bool((idx < 1024).any() and (idx >= 1024).any())
+    assert lo > 0 and hi > 0 and both > 0, (lo, hi, both)   # one step's list spans the chunk boundary
+    b.set_state({"step_counter": np.full(E, 10 ** 6)})
+    b.step(actions=b.actions * 0, autoreset=True, terminal_obs=True)
+    h = host.fetch()
+    assert _check_delivery(b, h) == E
+    assert np.array_equal(h["ended_env"], np.arange(E))
+    b.close()
+
+
 def test_vec_env_numpy_step_matches_tensor_step():
     """CattleHerdVecEnv.step (numpy in, pinned delivery out) and the same batch stepped with the same actions
     through the tensor path give the same observations, rewards, dones and terminal observations; the array a step
