@@ -715,6 +715,43 @@ int ch_ppo_train_log(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_p
                      int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats,
                      float* scratch, void* stream);
 
+/* Replaces: the rest of PPO.train's loop body that ch_ppo_train_log leaves out -- PPO(..., target_kl=, clip_range_vf=):
+ *   values_pred = old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf)   (clip_range_vf set)
+ *   if approx_kl > 1.5 * target_kl: continue_training = False; break                     (target_kl set)
+ * One call is one epoch, as ch_ppo_train_log; `opts` carries the two options and what they read.
+ * Value clipping: the clipped prediction enters the squared error (column 1 is then the clipped value loss), and a
+ * row with |values - old_values| > clip_range_vf gives the value head no gradient; a row exactly at the bound keeps
+ * it (torch.clamp's backward).
+ * The gate runs on the device, with no host synchronisation: the minibatch's approx_kl is column 4's float32 value,
+ * and every workgroup that needs the decision forms it from the same per-tile sums in the same order.  A minibatch
+ * that trips writes its statistics row, sets *stop_dev and changes nothing else: no weight, m, v, and *step_dev does
+ * not advance (SB3 breaks before the optimizer step).  With *stop_dev non-zero -- later minibatches of the call, and
+ * later calls handed the same word, the following epochs -- every launch returns at entry: weights, m, v, *step_dev
+ * and *stop_dev stay bit-for-bit as they were.
+ * stats is required: [steps][CH_PPO_OPT_STATS]; column 6, `state`: 1 the optimizer step was applied, 0 this
+ * minibatch tripped the gate (columns 0-5 valid, ch_ppo_train_log's), -1 not run because the gate had tripped
+ * (columns 0-5 NaN).  SB3's lists hold the rows with state >= 0; n_updates grows by the epochs with such a row.
+ * With both options off (<= 0) the weights, m, v, the step count and columns 0-5 are bit-identical to
+ * ch_ppo_train_log from the same state.  ch_ppo_scratch_size sizes the scratch; the flat gradient of the last
+ * minibatch that ran is its last region, param_count floats rounded up to a multiple of 4.
+ * CH_ERR_INVALID (nothing is launched) for NULL opts, clip_range_vf > 0 with NULL old_values, target_kl > 0 with NULL
+ * stop_dev.
+ * DIFFERENCE: SB3 compares np.mean of a float32 tensor's numpy array with the Python float 1.5 * target_kl; whether
+ * that comparison runs in float32 or float64 depends on the numpy version's promotion rules.  The device compares in
+ * float64: (double)approx_kl > 1.5 * target_kl, approx_kl being the float32 statistic.  A NaN approx_kl does not trip,
+ * as in SB3. */
+typedef struct ch_ppo_opts {
+    double target_kl;        /* <= 0: no gate (SB3 None) */
+    double clip_range_vf;    /* <= 0: no value clipping (SB3 None) */
+    const float* old_values; /* [data->rows], RolloutBuffer.values; required when clip_range_vf > 0 */
+    int32_t* stop_dev;       /* required when target_kl > 0: 0 = running, non-zero = stopped; the caller zeroes it
+                                before a train() and passes the same word to every epoch's call */
+} ch_ppo_opts;
+#define CH_PPO_OPT_STATS 7   /* CH_PPO_LOG_STATS columns, then `state` */
+int ch_ppo_train_opt(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const ch_ppo_opts* opts,
+                     const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
+                     float* stats, float* scratch, void* stream);
+
 /* Replaces: stable_baselines3.common.utils.explained_variance(rollout_buffer.values.flatten(),
  * rollout_buffer.returns.flatten()), PPO.train's train/explained_variance.  Handle-free; errors through
  * ch_last_error(NULL).  out_dev[0] = 1 - var(returns - values) / var(returns) with population variances (np.var), NaN

@@ -18,7 +18,8 @@ SOURCES = ["ch_kernels.hip", "ch_step.hip", "ch_step_multi.hip", "ch_policy.hip"
 # (ch_step_multi.hip header)
 SOURCE_FLAGS = {"ch_step_multi.hip": ["-mllvm", "-disable-machine-licm"]}
 HEADERS = ["ch_device.h", "ch_internal.h", "ch_common.h", "ch_spawn_table.inc", "ch_mlp2_dev.h", "ch_rollout_dev.h",
-           "ch_step_body.h", "ch_step_sync.h", "ch_step_flock.h", "ch_handle.h", "ch_ppo.h", "ch_mlp_plan.h"]
+           "ch_step_body.h", "ch_step_sync.h", "ch_step_flock.h", "ch_handle.h", "ch_ppo.h", "ch_ppo_fb_body.inc",
+           "ch_ppo_dw_body.inc", "ch_ppo_adam_body.inc", "ch_mlp_plan.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("CH_OFFLOAD_ARCH", "gfx950")
 # fp-contract off: the fp64 path keeps the reference's rounding (no fused multiply-adds), so it

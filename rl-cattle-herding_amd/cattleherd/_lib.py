@@ -32,7 +32,7 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark", "ch_eval_log_record", "ch_eval_log_run",
            "ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
            "ch_explained_variance_scratch", "ch_explained_variance", "ch_marl_ep_ring_begin", "ch_marl_ep_ring_record",
-           "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log")
+           "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log", "ch_ppo_train_opt")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
@@ -46,6 +46,9 @@ _MARL_TRAIN_LOG_EXPORTS = ("ch_marl_ep_ring_begin", "ch_marl_ep_ring_record", "c
 # ch_marl_ppo_train_log's columns: ch_marl_ppo_train's five, then vf_loss_unclipped, total_loss, vf_explained_var
 CH_MARL_PPO_LOG_STATS = 8
 CH_PPO_LOG_STATS = 6   # ch_ppo_train_log's columns: policy loss, value loss, mean entropy, grad norm, approx_kl, clip_fraction
+# target_kl / clip_range_vf (cattleherd/ppo.py): likewise
+_PPO_OPT_EXPORTS = ("ch_ppo_train_opt",)
+CH_PPO_OPT_STATS = 7   # ch_ppo_train_opt's columns: ch_ppo_train_log's six, then the step's state (1 applied, 0 tripped, -1 not run)
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -99,6 +102,11 @@ class ChPpoHparams(ctypes.Structure):
 class ChPpoData(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "actions", "old_log_prob", "advantages", "returns")] + \
         [("rows", ctypes.c_int64)]
+
+
+class ChPpoOpts(ctypes.Structure):
+    _fields_ = [("target_kl", ctypes.c_double), ("clip_range_vf", ctypes.c_double), ("old_values", ctypes.c_void_p),
+                ("stop_dev", ctypes.c_void_p)]
 
 
 class ChMarlPpoNet(ctypes.Structure):
@@ -258,7 +266,10 @@ def lib():
         L.ch_marl_ep_ring_begin.argtypes = [vp, P(ChMarlEpRing), vp]
         L.ch_marl_ep_ring_record.argtypes = [vp, P(ChMarlEpRing), vp, P(ChStepIO), vp]
         L.ch_marl_ppo_train_log.argtypes = L.ch_marl_ppo_train.argtypes
-    optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS
+    if hasattr(L, "ch_ppo_train_opt"):
+        L.ch_ppo_train_opt.argtypes = [P(ChPpoNet), P(ChPpoHparams), P(ChPpoData), P(ChPpoOpts), vp, i64, i64, vp, vp, vp,
+                                       vp, vp, vp]
+    optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS + _PPO_OPT_EXPORTS
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in optional or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int

@@ -65,13 +65,15 @@ class NativeState:
         self.step_count = torch.zeros(1, dtype=torch.int64, device=model.device)
         self.scratch = None
 
-    def train(self, hp, data, n_epochs, n, batch_size, draw, stats=None, log=False):
+    def train(self, hp, data, n_epochs, n, batch_size, draw, stats=None, log=False, opts=None):
         """``n_epochs`` calls of the flavour's ``*_train`` on the current stream of the model's device, each over the
         ``n`` row indices (int64, on the device) that ``draw()`` returns, in minibatches of ``batch_size``.  ``hp`` and
         ``data`` are the flavour's hparams and data structs; ``stats``: None or the per-step statistics' float32
         tensor ``[n_epochs * steps per epoch, k]``.  ``log``: ``*_train_log``, whose ``stats`` are required and
-        ``CH_PPO_LOG_STATS`` (SB3 flavour) / ``CH_MARL_PPO_LOG_STATS`` (RLlib flavour) wide.  Returns the number of
-        minibatch steps."""
+        ``CH_PPO_LOG_STATS`` (SB3 flavour) / ``CH_MARL_PPO_LOG_STATS`` (RLlib flavour) wide.  ``opts`` (SB3 flavour): a
+        ``ChPpoOpts`` -- every epoch is a ``ch_ppo_train_opt`` call with it, ``stats`` required and
+        ``CH_PPO_OPT_STATS`` wide; the caller has zeroed its stop word.  Returns the number of minibatch steps
+        (launched: with ``opts``' KL gate the later ones may not have run)."""
         import torch
         lib, dev = _lib.lib(), self.model.device
         net = net_struct(self.fl, self.model)   # the parameters' storage as it is now (a .to() or .data = ... moves it)
@@ -79,6 +81,9 @@ class NativeState:
         if self.scratch is None or self.scratch.numel() < want:
             self.scratch = torch.empty(want, dtype=torch.float32, device=dev)
         train = getattr(lib, self.fl.prefix + ("train_log" if log else "train"))
+        if opts is not None:
+            def train(net, hp, data, *rest, fn=lib.ch_ppo_train_opt, opts=ctypes.byref(opts)):
+                return fn(net, hp, data, opts, *rest)
         nb = (n + batch_size - 1) // batch_size
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream

@@ -6,7 +6,8 @@ with Monitor's ``info["episode"]`` step by step, in env order, inside ``collect_
 from ``PPO.train``.  ``EpisodeRing`` is that deque as a ring in device memory, appended to by one small kernel per step
 (``ch_ep_ring_record``; inside the native collection with ``DeviceRolloutBuffer.collect(..., ring=ring)``), read with
 one small copy when the record is wanted.  The ``train/`` half is ``PPOUpdate(..., log_stats=True)`` (cattleherd/ppo.py),
-over ``ch_ppo_train_log`` and ``explained_variance`` below.
+over ``ch_ppo_train_log`` (``ch_ppo_train_opt`` with ``target_kl`` / ``clip_range_vf``), ``explained_variance`` and
+``sb3_train_record`` below.
 
 Semantics restated from SB3 2.x; SB3 is not installed here, so the restatement is "parity unpinned" to its source.
 One difference is deliberate: SB3's ``explained_variance`` is float32 numpy, here the float32 inputs are widened
@@ -109,6 +110,45 @@ def explained_variance(values, returns, out=None):
         L.check(lib.ch_explained_variance(values.data_ptr(), returns.data_ptr(), n, out.data_ptr(), scratch.data_ptr(),
                                           torch.cuda.current_stream(dev).cuda_stream))
     return out
+
+
+def sb3_train_record(stats, steps_per_epoch, ent_coef, vf_coef, clip_range, explained_variance, std, n_updates=0,
+                     learning_rate=None, clip_range_vf=None):
+    """SB3 ``PPO.train``'s logger record from a call's per-minibatch statistics -- a pure host function.  ``stats``:
+    ``[steps, 6]`` (``ch_ppo_train_log``'s columns: policy loss, value loss, mean entropy, gradient norm, approx_kl,
+    clip_fraction) or ``[steps, 7]`` (``ch_ppo_train_opt``'s: then ``state``, 1 applied / 0 tripped the KL gate / -1
+    not run), epoch after epoch with ``steps_per_epoch`` rows each.  SB3 appends a minibatch's statistics before the
+    gate, so each key's ``np.mean`` runs over the rows with ``state >= 0``, the tripping one included, and
+    ``train/loss`` is the last such row's ``policy + ent_coef * entropy_loss + vf_coef * value`` (the value loss as the
+    row holds it: clipped with ``clip_range_vf``).  ``train/n_updates`` is ``n_updates`` plus the epochs that ran at
+    least one minibatch, the one that broke included.  ``train/learning_rate`` follows when ``learning_rate`` is given
+    and ``train/clip_range_vf`` when set.  Returns ``(record, epochs_run)``."""
+    st = np.asarray(stats, np.float64)
+    state = st[:, 6] if st.shape[1] > 6 else np.ones(len(st))
+    ran = state >= 0
+    if not ran.any():
+        raise ValueError("sb3_train_record: no minibatch ran (was the stop word zeroed before the call?)")
+    epochs_run = len({k // int(steps_per_epoch) for k in np.flatnonzero(ran)})
+    r = st[ran]
+    pl, vl, ent, akl, cf = r[:, 0], r[:, 1], r[:, 2], r[:, 4], r[:, 5]
+    # SB3: each list holds the minibatches' float32 .item()s; the logger records np.mean of each (float64)
+    rec = {
+        "train/entropy_loss": float(np.mean(-ent)),
+        "train/policy_gradient_loss": float(np.mean(pl)),
+        "train/value_loss": float(np.mean(vl)),
+        "train/approx_kl": float(np.mean(akl)),
+        "train/clip_fraction": float(np.mean(cf)),
+        "train/loss": float(pl[-1] + ent_coef * -ent[-1] + vf_coef * vl[-1]),   # the last minibatch's
+        "train/explained_variance": float(explained_variance),
+        "train/std": float(std),
+        "train/n_updates": int(n_updates) + epochs_run,
+        "train/clip_range": float(clip_range),
+    }
+    if learning_rate is not None:
+        rec["train/learning_rate"] = float(learning_rate)
+    if clip_range_vf is not None:
+        rec["train/clip_range_vf"] = float(clip_range_vf)
+    return rec, epochs_run
 
 
 # ---- the DTDE (MARL) driver: RLlib's result dict ----------------------------------------------------------------

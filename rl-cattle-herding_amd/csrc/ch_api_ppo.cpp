@@ -250,6 +250,42 @@ int train(const typename F::Net* net, const typename F::Hparams* hp, const typen
     return CH_OK;
 }
 
+// ch_ppo_train_opt (SB3 flavour only): train<Sb3> with log_stats, through the option kernels
+int train_opt(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const ch_ppo_opts* opts,
+              const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats,
+              float* scratch, void* stream) {
+    const std::string w = who<Sb3>("train_opt");
+    if (!net || !hp || !data || !idx || !m || !v || !step_dev || !scratch || !stats)
+        return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
+    if (!opts) return fail(nullptr, CH_ERR_INVALID, w + "NULL opts");
+    if (opts->clip_range_vf > 0.0 && !opts->old_values) return fail(nullptr, CH_ERR_INVALID, w + "clip_range_vf > 0 needs old_values");
+    if (opts->target_kl > 0.0 && !opts->stop_dev) return fail(nullptr, CH_ERR_INVALID, w + "target_kl > 0 needs stop_dev");
+    PpoNet n;
+    PpoData d;
+    std::string err;
+    int rc;
+    if ((rc = to_net<Sb3>(net, true, n, err)) || (rc = to_data<Sb3>(data, hp, d, err))) return fail(nullptr, rc, w + err);
+    if (n_idx < 1 || batch_size < 1 || batch_size > kMaxBatch) return fail(nullptr, CH_ERR_INVALID, w + "n_idx >= 1 and batch_size 1..2^24 required");
+    if (misaligned(scratch)) return fail(nullptr, CH_ERR_INVALID, w + "scratch must be 16-byte aligned");
+    PpoScratch s;
+    ppo_scratch_layout(n, std::min(batch_size, n_idx), s);
+    const PpoHp h = Sb3::hp(hp);
+    const PpoOpt o{opts->target_kl, opts->clip_range_vf, opts->old_values, opts->stop_dev};
+    hipStream_t st = (hipStream_t)stream;
+    long long* step = reinterpret_cast<long long*>(step_dev);
+    int64_t k = 0;
+    for (int64_t j = 0; j < n_idx; j += batch_size, ++k) {
+        const int64_t batch = std::min(batch_size, n_idx - j);
+        PpoScratch sj = s;
+        sj.tiles = (int)((batch + kPpoTile - 1) / kPpoTile);
+        sj.bp = sj.tiles * kPpoTile;
+        const hipError_t e = ppo_launch_step_opt(n, h, d, o, reinterpret_cast<const long long*>(idx) + j, batch, m, v, step,
+                                                 scratch, sj, stats + CH_PPO_OPT_STATS * k, st);
+        if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
+    }
+    return CH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -277,6 +313,12 @@ int ch_ppo_train_log(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_p
                      int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
                      void* stream) {
     return train<Sb3>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream, true);
+}
+
+int ch_ppo_train_opt(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const ch_ppo_opts* opts,
+                     const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
+                     float* stats, float* scratch, void* stream) {
+    return train_opt(net, hp, data, opts, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
 }
 
 int64_t ch_marl_ppo_param_count(const ch_marl_ppo_net* net) { return param_count<Rllib>(net); }

@@ -97,6 +97,21 @@ hipError_t ppo_launch_sumsq(const PpoNet& n, const float* grad, float* scratch, 
 hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, float* m, float* v,
                            const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
                            float* stats, hipStream_t st, bool log_stats = false);
+
+// ch_ppo_train_opt's options (kPpoSb3): SB3's target_kl and clip_range_vf, <= 0 for None.
+struct PpoOpt {
+    double target_kl, clip_range_vf;
+    const float* old_values;   // [rows], read when clip_range_vf > 0
+    int32_t* stop_dev;         // the stop word, read and set when target_kl > 0
+};
+// One minibatch step of ch_ppo_train_opt: the three launches of ppo_launch_grad + ppo_launch_adam with log_stats, as
+// their option variants (ch_ppo.hip: k_ppo_fb_opt, k_ppo_dw_opt, k_ppo_adam_opt) over the gradient region of
+// `scratch`.  stats7: this step's row of CH_PPO_OPT_STATS.  With the stop word set the launches return at entry (the
+// Adam launch leaves the row NaN with state -1); a minibatch whose approx_kl exceeds 1.5 * target_kl writes its
+// statistics, sets the word and updates nothing, *step_dev included.
+hipError_t ppo_launch_step_opt(const PpoNet& n, const PpoHp& hp, const PpoData& d, const PpoOpt& opt, const long long* idx,
+                               long long batch, float* m, float* v, long long* step_dev, float* scratch,
+                               const PpoScratch& s, float* stats7, hipStream_t st);
 hipError_t ppo_launch_stats(const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
                             float* stats, hipStream_t st);
 

@@ -24,6 +24,11 @@
 // ch_marl_ppo_train_log a fourth flavour (kPpoRllibLog) of k_ppo_fb and k_ppo_adam adds RLlib's vf_loss_unclipped,
 // total_loss and vf_explained_var.
 //
+// ch_ppo_train_opt (SB3's target_kl and clip_range_vf) has kernels of its own -- k_ppo_fb_opt, k_ppo_dw_opt,
+// k_ppo_adam_opt -- over the same three bodies, which live in ch_ppo_{fb,dw,adam}_body.inc and are included into the
+// plain and the option kernels alike (Options): the stop word's early return, the clipped value
+// prediction, and the KL gate that every workgroup decides for itself from the same scratch sums.
+//
 // MFMA operand map (16x16x4 f32): lane l gives A[row l & 15][k slot l >> 4] and B[k slot l >> 4][col l & 15]; it
 // holds C/D[row 4 (l >> 4) + r][col l & 15] in register r.  Which k a slot stands for is free as long as A and B
 // agree, so a lane loads four consecutive k as one float4 and feeds element j to the j-th MFMA of the chunk.
@@ -32,6 +37,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "ch_ppo.h"
 
@@ -162,6 +168,42 @@ constexpr int kFbSb3Log = 2;
 // Kernels of their own, so that ch_marl_ppo_train launches what it launched before.
 constexpr int kPpoRllibLog = 3;
 constexpr bool ppo_rllib(int F) { return F == kPpoRllib || F == kPpoRllibLog; }
+// the fifth and sixth, of k_ppo_fb (ch_ppo_train_opt): kFbSb3Log behind the stop word's early return, and that with
+// SB3's clip_range_vf.  Kernels of their own again (k_ppo_fb_opt): the four above stay the code they were.
+constexpr int kFbSb3Opt = 4;
+constexpr int kFbSb3OptVf = 5;
+constexpr bool fb_opt(int F) { return F == kFbSb3Opt || F == kFbSb3OptVf; }
+
+// What ch_ppo_train_opt's kernels take beside the arguments of the plain ones.  NoOpt: the plain
+// kernels, whose bodies compile to what they were.
+struct NoOpt {};
+// NoOpt as a type that depends on the flavour, so that a plain kernel's discarded `if constexpr` branches, which name
+// the options' members, are not looked up in it
+template <int F, class Opt>
+using PlainOpt = std::conditional_t<(F >= 0), NoOpt, Opt>;
+struct FbOpt {
+    const int32_t* stop;       // NULL: no gate
+    const float* old_values;   // kFbSb3OptVf: [rows], the rollout's value predictions
+    float clip_vf;             // kFbSb3OptVf: clip_range_vf
+};
+// The KL gate.  `stop` is the call's stop word (NULL: no gate): non-zero means an earlier minibatch tripped, and every
+// launch returns at entry.  Otherwise a workgroup that needs this minibatch's decision forms it itself with
+// gate_trips: the same float32 sums over the same scratch values in the same order as the approx_kl statistic, so all
+// of them -- the weight-gradient launch's thread that counts the Adam step, every Adam workgroup -- agree without
+// waiting for one another.
+struct GateArgs {
+    int32_t* stop;
+    const float* tile_stat;    // this minibatch's tile partials (k_ppo_fb wrote them; a kernel boundary lies between)
+    double threshold;          // 1.5 * target_kl
+};
+
+// approx_kl exactly as k_ppo_adam's statistic: the tiles' sums in index order, divided by the batch, compared in float64
+__device__ __forceinline__ bool gate_trips(const GateArgs& g, int tiles, long long batch) {
+    if (!g.stop) return false;
+    float akl = 0.0f;
+    for (int t = 0; t < tiles; ++t) akl += g.tile_stat[2 * tiles + 2 * t];
+    return (double)(akl / (float)batch) > g.threshold;
+}
 
 // per-tile loss partials: the surrogate and the squared value error; kPpoRllib adds the entropy and the KL
 template <int F>
@@ -169,265 +211,13 @@ constexpr int kStat = ppo_rllib(F) ? 4 : 2;
 
 template <int F>
 __global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb(FbArgs a) {
-    [[maybe_unused]] constexpr bool kLog = F == kFbSb3Log;
-    __shared__ __align__(16) float hs[2][kPpoTile * kLdh];   // hidden activations
-    __shared__ __align__(16) float dzs[kPpoTile * kLdh];     // dZ of the last hidden layer
-    __shared__ __align__(16) float os[kPpoTile * kLdo];      // the head's output, then its dZ
-    __shared__ float tmp[kPpoTile * kLdo];                   // per-row log_std gradient terms
-    __shared__ float red[kFbWaves];
-    __shared__ float rowstat[kPpoTile];
-    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, ni = blockIdx.y;
-    const PpoMlp& net = a.n.net[ni];
-    const int L = net.layers, B = (int)a.batch;
-    const long long row0 = (long long)tile * kPpoTile;
-    const float inv_b = 1.0f / (float)B;
+    [[maybe_unused]] constexpr PlainOpt<F, FbOpt> o{};
+#include "ch_ppo_fb_body.inc"
+}
 
-    // the minibatch's advantage statistics (policy net only): torch's mean and unbiased std, two passes
-    float adv_mean = 0.0f, adv_scale = 1.0f;
-    if (ni == 0 && a.normalize && B > 1) {
-        float s = 0.0f;
-        for (int i = tid; i < B; i += 64 * kFbWaves) s += a.d.advantages[a.idx[i]];
-        adv_mean = block_sum(s, red, kFbWaves) * inv_b;
-        float q = 0.0f;
-        for (int i = tid; i < B; i += 64 * kFbWaves) {
-            const float t = a.d.advantages[a.idx[i]] - adv_mean;
-            q += t * t;
-        }
-        const float var = block_sum(q, red, kFbWaves) / (float)(B - 1);
-        adv_scale = 1.0f / (sqrtf(var) + 1e-8f);
-    }
-
-    // forward.  Rows past the minibatch read its last row: finite values that meet dZ = 0.
-    const long long my_row = a.idx[min(row0 + c, a.batch - 1)];
-    const float* xrow = a.d.obs + my_row * a.n.obs_dim;
-    for (int li = 0; li < L; ++li) {
-        const int K = net.dims[li], N = net.dims[li + 1];
-        const bool head = li == L - 1;
-        const float* arow = li == 0 ? xrow : hs[li - 1] + c * kLdh;
-        // (hidden activations: aligned LDS rows; readfirstlane: the branch around the MFMA loop stays scalar)
-        const bool vec = __builtin_amdgcn_readfirstlane(a.vec_w[ni][li] && (li > 0 || a.vec_obs)) != 0;
-        for (int t = wave; t < (N + 15) / 16; t += kFbWaves) {
-            const int col = t * 16 + c;
-            const f32x4 acc = fwd_tile(arow, net.w[li] + (long long)min(col, N - 1) * K, vec, K);
-            if (col < N) {
-                const float bv = net.b[li][col];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 4 * g + r;
-                    const float z = acc[r] + bv;
-                    if (head) {
-                        os[row * kLdo + col] = z;
-                    } else {
-                        const float h = tanhf(z);
-                        hs[li][row * kLdh + col] = h;
-                        a.scratch[a.s.act[ni][li] + (row0 + row) * N + col] = h;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    // the loss and its gradient with respect to the head's output, rows past the minibatch 0
-    const int NO = net.dims[L];
-    if constexpr (ppo_rllib(F)) {
-        if (ni == 0) {
-            // 16 lanes per row.  The head is [mean (A), raw log_std (A)], log_std = the raw value clamped to +-ls_clip
-            // (torch.clamp: the gradient passes inside the closed range).  Per row: the log-probability of the stored
-            // action, the entropy, and KL(sampling policy || this one) against the gathered old dist inputs.
-            const int row = tid >> 4, sub = tid & 15, A = NO >> 1;
-            if (row < kPpoTile) {
-                const bool valid = row0 + row < a.batch;
-                const long long src = a.idx[min(row0 + row, a.batch - 1)];
-                float lp = 0.0f, ent = 0.0f, kl = 0.0f;
-                for (int j = sub; j < A; j += 16) {
-                    const float mu = os[row * kLdo + j];
-                    const float ls = fminf(fmaxf(os[row * kLdo + A + j], -a.ls_clip), a.ls_clip);
-                    const float mu_p = a.d.old_dist[src * NO + j], ls_p = a.d.old_dist[src * NO + A + j];
-                    const float var = expf(2.0f * ls), dlt = a.d.actions[src * A + j] - mu, dm = mu_p - mu;
-                    lp += -(dlt * dlt) / (2.0f * var) - ls - kHalfLog2Pi;
-                    ent += ls + 0.5f + kHalfLog2Pi;
-                    kl += ls - ls_p + (expf(2.0f * ls_p) + dm * dm) / (2.0f * var) - 0.5f;
-                }
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) {
-                    lp += __shfl_xor(lp, o);
-                    ent += __shfl_xor(ent, o);
-                    kl += __shfl_xor(kl, o);
-                }
-                const float adv = a.d.advantages[src];   // standardised once per training iteration by the caller
-                const float ratio = expf(lp - a.d.old_log_prob[src]);
-                const float s1 = adv * ratio;
-                const float s2 = adv * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
-                const float dlp = valid && s1 <= s2 ? -inv_b * adv * ratio : 0.0f;   // (torch.min: see kPpoSb3 below)
-                const float klc = valid ? *a.kl_coeff_dev * inv_b : 0.0f, entc = valid ? a.ent_coef * inv_b : 0.0f;
-                if (sub == 0) {
-                    rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
-                    tmp[row] = valid ? ent : 0.0f;
-                    tmp[kPpoTile + row] = valid ? kl : 0.0f;
-                }
-                for (int j = sub; j < A; j += 16) {   // (each lane reads, then overwrites, its own columns)
-                    const float mu = os[row * kLdo + j], raw = os[row * kLdo + A + j];
-                    const float ls = fminf(fmaxf(raw, -a.ls_clip), a.ls_clip);
-                    const float mu_p = a.d.old_dist[src * NO + j], ls_p = a.d.old_dist[src * NO + A + j];
-                    const float var = expf(2.0f * ls), dlt = a.d.actions[src * A + j] - mu, dm = mu_p - mu;
-                    const float dls = dlp * (dlt * dlt / var - 1.0f) - entc + klc * (1.0f - (expf(2.0f * ls_p) + dm * dm) / var);
-                    os[row * kLdo + j] = dlp * dlt / var - klc * dm / var;
-                    os[row * kLdo + A + j] = raw >= -a.ls_clip && raw <= a.ls_clip ? dls : 0.0f;
-                }
-            }
-        } else if (tid < kPpoTile) {
-            // clamp((V - R)^2, 0, vf_clip): the gradient passes where the squared error is inside the closed range
-            const bool valid = row0 + tid < a.batch;
-            const long long src = a.idx[min(row0 + tid, a.batch - 1)];
-            const float err = os[tid * kLdo] - a.d.returns[src], e2 = err * err;
-            if constexpr (F == kPpoRllibLog) {
-                // the training log's share of the row: the squared error before the clamp (`tmp` is free in a critic
-                // workgroup), and the value and its target as the loss used them, for the explained variance
-                tmp[tid] = valid ? e2 : 0.0f;
-                float* vy = a.scratch + a.s.misc + 4 + a.s.tiles + 2 * (row0 + tid);
-                vy[0] = os[tid * kLdo];
-                vy[1] = a.d.returns[src];
-            }
-            rowstat[tid] = valid ? fminf(e2, a.vf_clip) : 0.0f;
-            os[tid * kLdo] = valid && e2 <= a.vf_clip ? a.vf_coef * 2.0f * err * inv_b : 0.0f;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            float s = 0.0f, e = 0.0f, k = 0.0f;
-            for (int r = 0; r < kPpoTile; ++r) s += rowstat[r];
-            a.scratch[a.s.tile_stat + 4 * tile + ni] = s;
-            if (ni == 0) {
-                for (int r = 0; r < kPpoTile; ++r) {
-                    e += tmp[r];
-                    k += tmp[kPpoTile + r];
-                }
-                a.scratch[a.s.tile_stat + 4 * tile + 2] = e;
-                a.scratch[a.s.tile_stat + 4 * tile + 3] = k;
-            }
-            if (F == kPpoRllibLog && ni == 1) {   // the tile's unclipped squared errors, rows in order
-                float u = 0.0f;
-                for (int r = 0; r < kPpoTile; ++r) u += tmp[r];
-                a.scratch[a.s.misc + 4 + tile] = u;
-                if (tile == 0) {   // and the loss's coefficients, as this kernel used them
-                    a.scratch[a.s.misc] = a.vf_coef;
-                    a.scratch[a.s.misc + 1] = a.ent_coef;
-                    a.scratch[a.s.misc + 2] = *a.kl_coeff_dev;
-                }
-            }
-        }
-    } else {
-        if (ni == 0) {
-            // 16 lanes per row: log-probability of the stored action under N(mean, exp(log_std))
-            const int row = tid >> 4, sub = tid & 15;
-            if (row < kPpoTile) {
-                const bool valid = row0 + row < a.batch;
-                const long long src = a.idx[min(row0 + row, a.batch - 1)];
-                float lp = 0.0f;
-                // (lp64, kFbSb3Log: the same log-probability from the same float32 mean, widened exactly and summed in
-                // float64, for approx_kl alone -- see below; the loss keeps the float32 one)
-                double lp64 = 0.0;
-                for (int j = sub; j < NO; j += 16) {
-                    const float ls = a.n.log_std[j], dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
-                    lp += -(dlt * dlt) / (2.0f * expf(2.0f * ls)) - ls - kHalfLog2Pi;
-                    if constexpr (kLog) {
-                        const double ls64 = ls, d64 = (double)a.d.actions[src * NO + j] - (double)os[row * kLdo + j];
-                        lp64 += -(d64 * d64) / (2.0 * exp(2.0 * ls64)) - ls64 - kHalfLog2Pi64;
-                    }
-                }
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) {
-                    lp += __shfl_xor(lp, o);
-                    if constexpr (kLog) lp64 += __shfl_xor(lp64, o);
-                }
-                float adv = a.d.advantages[src];
-                if (a.normalize && B > 1) adv = (adv - adv_mean) * adv_scale;
-                const float log_ratio = lp - a.d.old_log_prob[src];
-                const float ratio = expf(log_ratio);
-                const float s1 = adv * ratio;
-                const float s2 = adv * fminf(fmaxf(ratio, 1.0f - a.clip_range), 1.0f + a.clip_range);
-                // torch.min's gradient goes to the smaller branch (both when they tie: inside the clip range, where the
-                // clamp passes it on); the clamped branch outside the range has none
-                const float dlp = valid && s1 <= s2 ? -inv_b * adv * ratio : 0.0f;
-                if (sub == 0) {
-                    rowstat[row] = valid ? fminf(s1, s2) : 0.0f;
-                    if constexpr (kLog) {
-                        // SB3's diagnostics of the row (PPO.train's approx_kl_divs and clip_fractions), in the two
-                        // columns of `tmp` past the widest head: (ratio - 1) - log_ratio, and |ratio - 1| > clip_range
-                        // as 0 / 1.  The first cancels: it is ~log_ratio^2 / 2, so the float32 rounding of a
-                        // log-probability of magnitude 10-20 and of the ratio is ~1e-5 of it in a one-row minibatch.
-                        // It is evaluated in float64 from lp64 and rounded once; the clip test is the loss's own ratio.
-                        const double lr64 = lp64 - (double)a.d.old_log_prob[src];
-                        tmp[row * kLdo + kPpoMaxAct] = valid ? (float)(expm1(lr64) - lr64) : 0.0f;
-                        tmp[row * kLdo + kPpoMaxAct + 1] = valid && fabsf(ratio - 1.0f) > a.clip_range ? 1.0f : 0.0f;
-                    }
-                }
-                for (int j = sub; j < NO; j += 16) {
-                    const float var = expf(2.0f * a.n.log_std[j]);
-                    const float dlt = a.d.actions[src * NO + j] - os[row * kLdo + j];
-                    tmp[row * kLdo + j] = dlp * (dlt * dlt / var - 1.0f);
-                    os[row * kLdo + j] = dlp * dlt / var;   // d loss / d mean (each lane its own columns)
-                }
-            }
-        } else if (tid < kPpoTile) {
-            const bool valid = row0 + tid < a.batch;
-            const long long src = a.idx[min(row0 + tid, a.batch - 1)];
-            const float err = os[tid * kLdo] - a.d.returns[src];
-            rowstat[tid] = valid ? err * err : 0.0f;
-            os[tid * kLdo] = valid ? a.vf_coef * 2.0f * err * inv_b : 0.0f;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            float s = 0.0f;
-            for (int r = 0; r < kPpoTile; ++r) s += rowstat[r];
-            a.scratch[a.s.tile_stat + 2 * tile + ni] = s;
-            if (kLog && ni == 0) {   // the tile's diagnostics, rows in order, behind the [tiles][2] loss partials
-                float kl = 0.0f, cf = 0.0f;
-                for (int r = 0; r < kPpoTile; ++r) {
-                    kl += tmp[r * kLdo + kPpoMaxAct];
-                    cf += tmp[r * kLdo + kPpoMaxAct + 1];
-                }
-                a.scratch[a.s.tile_stat + 2 * a.s.tiles + 2 * tile] = kl;
-                a.scratch[a.s.tile_stat + 2 * a.s.tiles + 2 * tile + 1] = cf;
-            }
-            if (ni == 0 && tile == 0) {
-                float e = 0.0f;
-                for (int j = 0; j < NO; ++j) e += 0.5f + kHalfLog2Pi + a.n.log_std[j];
-                a.scratch[a.s.misc] = e;   // the entropy is the same for every row
-            }
-        }
-        if (ni == 0 && tid < NO) {
-            float s = 0.0f;
-            for (int r = 0; r < kPpoTile; ++r) s += tmp[r * kLdo + tid];
-            a.scratch[a.s.tile_dls + (long long)tile * NO + tid] = s;
-        }
-    }
-    for (int i = tid; i < kPpoTile * NO; i += 64 * kFbWaves) {
-        const int r = i / NO, j = i - r * NO;
-        a.scratch[a.s.dz[ni][L - 1] + (row0 + r) * NO + j] = os[r * kLdo + j];
-    }
-
-    // backward through the hidden layers: dZ[li] = (dZ[li + 1] W[li + 1]) (1 - h^2)
-    for (int li = L - 2; li >= 0; --li) {
-        const int H = net.dims[li + 1], N = net.dims[li + 2];
-        const float* dz_in = li == L - 2 ? os : dzs;
-        const int ld_in = li == L - 2 ? kLdo : kLdh;
-        for (int t = wave; t < H / 16; t += kFbWaves) {
-            const int col = t * 16 + c;
-            const f32x4 acc = bwd_tile(dz_in, ld_in, N, net.w[li + 1], H, t * 16);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 4 * g + r;
-                const float h = hs[li][row * kLdh + col];
-                const float dz = acc[r] * (1.0f - h * h);
-                if (li > 0) dzs[row * kLdh + col] = dz;   // (read by the next pass: the first pass reads `os`)
-                a.scratch[a.s.dz[ni][li] + (row0 + row) * H + col] = dz;
-            }
-        }
-        __syncthreads();
-    }
+template <int F>
+__global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb_opt(FbArgs a, FbOpt o) {
+#include "ch_ppo_fb_body.inc"
 }
 
 // one weight matrix's gradient: dW[N][K] = dz[bp][N]^T act[bp][K]
@@ -487,72 +277,15 @@ __device__ __forceinline__ void dw_loop(const DwArgs& a, const DwGemm& G, int n0
 
 template <int F>
 __global__ __launch_bounds__(64 * kDwWaves) void k_ppo_dw(DwArgs a) {
-    __shared__ float red[kDwWaves];
-    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wg = blockIdx.x;
-    if (wg == 0 && tid == 0 && a.step_dev) *a.step_dev += 1;   // the Adam step this gradient is for
-    float ss = 0.0f;
-    if (F == kPpoSb3 && wg == a.wg_ls) {   // (kPpoRllib: log_std is a head output, its gradient part of the GEMMs)
-        // log_std: the tiles' partials in order, and the entropy bonus (-ent_coef * mean entropy: -ent_coef each)
-        if (tid < a.act_dim) {
-            float s = 0.0f;
-            for (int t = 0; t < a.tiles; ++t) s += a.tile_dls[(long long)t * a.act_dim + tid];
-            s -= a.ent_coef;
-            a.g_ls[tid] = s;
-            ss = s * s;
-        }
-    } else {
-        int gi = 0;
-        for (int i = 1; i < a.ng; ++i)
-            if (wg >= a.g[i].wg0) gi = i;
-        const DwGemm& G = a.g[gi];
-        const int local = wg - G.wg0, nt = local / G.kgroups, kg = local - nt * G.kgroups;
-        // wave-uniform by construction (blockIdx, kernel arguments); readfirstlane keeps the branches around the
-        // MFMA loops scalar, so that every lane takes part in them
-        const int N = __builtin_amdgcn_readfirstlane(G.N), K = __builtin_amdgcn_readfirstlane(G.K);
-        const bool gather = __builtin_amdgcn_readfirstlane(G.act == nullptr) != 0;
-        const bool vec_act = __builtin_amdgcn_readfirstlane(G.vec_act) != 0;
-        const int n0 = 16 * nt, kw0 = __builtin_amdgcn_readfirstlane(kg * kDwCols + wave * 64);
-        if (kw0 < K) {
-            f32x4 acc[4];   // (dw_loop: register r of accumulator j is dW[n0 + 4 g + r][kw0 + 4 c + j])
-            float bsum;
-            if (gather) {
-                if (vec_act) dw_loop<true, true>(a, G, n0, kw0, acc, bsum);
-                else dw_loop<false, true>(a, G, n0, kw0, acc, bsum);
-            } else if (vec_act) {
-                dw_loop<true, false>(a, G, n0, kw0, acc, bsum);
-            } else {
-                dw_loop<false, false>(a, G, n0, kw0, acc, bsum);
-            }
-            const int k = kw0 + 4 * c;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + 4 * g + r;
-                if (n >= N) continue;
-                float* dst = G.gw + (long long)n * K + k;
-                if (G.vec_out && k < K) {
-                    *reinterpret_cast<float4*>(dst) = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (k + j < K) dst[j] = acc[j][r];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (k + j < K) ss += acc[j][r] * acc[j][r];
-            }
-            // the bias: the column sums of dz, the four row classes in the order (0 + 1) + (2 + 3)
-            float t = bsum + __shfl_xor(bsum, 16);
-            t += __shfl_xor(t, 32);
-            if (kg == 0 && wave == 0 && g == 0 && n0 + c < N) {
-                G.gb[n0 + c] = t;
-                ss += t * t;
-            }
-        }
-    }
-    const float total = block_sum(ss, red, kDwWaves);
-    if (tid == 0) a.partial[wg] = total;
+    using Gate = PlainOpt<F, GateArgs>;
+    [[maybe_unused]] constexpr Gate gate{};
+#include "ch_ppo_dw_body.inc"
+}
+
+__global__ __launch_bounds__(64 * kDwWaves) void k_ppo_dw_opt(DwArgs a, GateArgs gate) {
+    using Gate = GateArgs;
+    constexpr int F = kPpoSb3;
+#include "ch_ppo_dw_body.inc"
 }
 
 // the sum-of-squares partials of a given flat gradient (ch_ppo_adam)
@@ -644,73 +377,15 @@ __device__ __forceinline__ void rllib_log_stats(const AdamArgs& a) {
 
 template <int F>
 __global__ __launch_bounds__(256) void k_ppo_adam(AdamArgs a) {
-    __shared__ float red[4];
-    __shared__ float sc[4];
-    const int tid = threadIdx.x;
-    float s = 0.0f;
-    for (int i = tid; i < a.n_partials; i += 256) s += a.partial[i];
-    const float sumsq = block_sum(s, red, 4);
-    const float norm = sqrtf(sumsq);
-    if (blockIdx.x == 0 && tid == 0 && a.stats4) {
-        float pl = 0.0f, vl = 0.0f, en = 0.0f, kl = 0.0f;
-        for (int t = 0; t < a.tiles; ++t) {
-            pl += a.tile_stat[kStat<F> * t];
-            vl += a.tile_stat[kStat<F> * t + 1];
-            if constexpr (ppo_rllib(F)) {
-                en += a.tile_stat[4 * t + 2];
-                kl += a.tile_stat[4 * t + 3];
-            }
-        }
-        a.stats4[0] = -pl / (float)a.batch;
-        a.stats4[1] = vl / (float)a.batch;
-        if constexpr (ppo_rllib(F)) {
-            a.stats4[2] = en / (float)a.batch;
-            a.stats4[3] = kl / (float)a.batch;
-            a.stats4[4] = norm;
-        } else {
-            a.stats4[2] = a.misc[0];
-            a.stats4[3] = norm;
-            if (a.update & 2) {   // the tiles' diagnostics in index order (k_ppo_fb wrote them behind the loss partials)
-                float akl = 0.0f, cf = 0.0f;
-                for (int t = 0; t < a.tiles; ++t) {
-                    akl += a.tile_stat[2 * a.tiles + 2 * t];
-                    cf += a.tile_stat[2 * a.tiles + 2 * t + 1];
-                }
-                a.stats4[4] = akl / (float)a.batch;
-                a.stats4[5] = cf / (float)a.batch;
-            }
-        }
-    }
-    if constexpr (F == kPpoRllibLog) {
-        if (blockIdx.x == 0 && (a.update & 2)) rllib_log_stats(a);   // (ch_marl_ppo_train_log: stats4 is required)
-    }
-    if (!a.update) return;
-    if (tid == 0) {
-        // torch Adam's scalars in double, as its (non-capturable) step computes them on the host
-        const double t = (double)*a.step_dev;
-        const double bc1 = 1.0 - pow(a.beta1, t), bc2 = 1.0 - pow(a.beta2, t);
-        sc[0] = (float)fmin(1.0, a.max_grad_norm / ((double)norm + 1e-6));   // clip_grad_norm_
-        if (ppo_rllib(F) && !(a.max_grad_norm > 0.0)) sc[0] = 1.0f;     // grad_clip None
-        sc[1] = (float)(a.lr / bc1);
-        sc[2] = (float)(1.0 / sqrt(bc2));
-    }
-    __syncthreads();
-    const float coef = sc[0], step_size = sc[1], inv_sqrt_bc2 = sc[2];
-    const float b2 = (float)a.beta2, w1 = (float)(1.0 - a.beta1), w2 = (float)(1.0 - a.beta2);
-    const float eps = (float)a.eps;
-    for (long long i = (long long)blockIdx.x * 256 + tid; i < a.n_params; i += (long long)gridDim.x * 256) {
-        int si = 0;
-        for (int j = 1; j < a.nseg; ++j)
-            if (i >= a.seg[j].off) si = j;
-        float* p = a.seg[si].p + (i - a.seg[si].off);
-        const float gr = a.grad[i] * coef;
-        const float m = a.m[i] + (gr - a.m[i]) * w1;          // exp_avg.lerp_(grad, 1 - beta1)
-        const float v = a.v[i] * b2 + w2 * gr * gr;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        a.m[i] = m;
-        a.v[i] = v;
-        const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-        *p = *p - step_size * (m / denom);
-    }
+    using Gate = PlainOpt<F, GateArgs>;
+    [[maybe_unused]] constexpr Gate gate{};
+#include "ch_ppo_adam_body.inc"
+}
+
+__global__ __launch_bounds__(256) void k_ppo_adam_opt(AdamArgs a, GateArgs gate) {
+    using Gate = GateArgs;
+    constexpr int F = kPpoSb3;
+#include "ch_ppo_adam_body.inc"
 }
 
 int dw_tiles(int n) { return (n + 15) / 16; }
@@ -750,10 +425,10 @@ void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s) {
     s.total = o;
 }
 
-hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
-                           float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
-                           hipStream_t st, bool log_stats) {
-    FbArgs f;
+namespace {
+
+void fb_args(FbArgs& f, const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
+             float* scratch, const PpoScratch& s) {
     std::memset(&f, 0, sizeof(f));
     f.n = n; f.d = d; f.idx = idx; f.batch = batch; f.scratch = scratch; f.s = s;
     f.clip_range = (float)hp.clip_range; f.vf_coef = (float)hp.vf_coef;
@@ -763,14 +438,11 @@ hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, c
     f.vec_obs = n.obs_dim % 4 == 0 && aligned16(d.obs);
     for (int ni = 0; ni < 2; ++ni)
         for (int li = 0; li < n.net[ni].layers; ++li) f.vec_w[ni][li] = n.net[ni].dims[li] % 4 == 0 && aligned16(n.net[ni].w[li]);
-    const bool rllib = n.flavour == kPpoRllib;
-    hipLaunchKernelGGL(rllib ? (log_stats ? k_ppo_fb<kPpoRllibLog> : k_ppo_fb<kPpoRllib>)
-                             : (log_stats ? k_ppo_fb<kFbSb3Log> : k_ppo_fb<kPpoSb3>),
-                       dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+}
 
-    DwArgs w;
+// returns the weight-gradient grid: one sum-of-squares partial per workgroup
+int dw_args(DwArgs& w, const FbArgs& f, const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx,
+            long long batch, float* grad, float* scratch, const PpoScratch& s, long long* step_dev) {
     std::memset(&w, 0, sizeof(w));
     int wg = 0;
     for (int ni = 0; ni < 2; ++ni) {
@@ -788,10 +460,29 @@ hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, c
             wg += dw_tiles(G.N) * G.kgroups;
         }
     }
-    w.wg_ls = rllib ? -1 : wg++;
+    w.wg_ls = n.flavour == kPpoRllib ? -1 : wg++;
     w.obs = d.obs; w.idx = idx; w.batch = batch; w.bp = s.bp; w.tiles = s.tiles; w.act_dim = n.act_dim;
     w.tile_dls = scratch + s.tile_dls; w.g_ls = grad + n.goff_log_std; w.ent_coef = (float)hp.ent_coef;
     w.partial = scratch + s.partial; w.step_dev = step_dev;
+    return wg;
+}
+
+}  // namespace
+
+hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
+                           float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
+                           hipStream_t st, bool log_stats) {
+    FbArgs f;
+    fb_args(f, n, hp, d, idx, batch, scratch, s);
+    const bool rllib = n.flavour == kPpoRllib;
+    hipLaunchKernelGGL(rllib ? (log_stats ? k_ppo_fb<kPpoRllibLog> : k_ppo_fb<kPpoRllib>)
+                             : (log_stats ? k_ppo_fb<kFbSb3Log> : k_ppo_fb<kPpoSb3>),
+                       dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    DwArgs w;
+    const int wg = dw_args(w, f, n, hp, d, idx, batch, grad, scratch, s, step_dev);
     hipLaunchKernelGGL(rllib ? k_ppo_dw<kPpoRllib> : k_ppo_dw<kPpoSb3>, dim3((unsigned)wg), dim3(64 * kDwWaves), 0, st, w);
     *n_partials = wg;
     return hipGetLastError();
@@ -833,6 +524,36 @@ hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, 
     const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
     hipLaunchKernelGGL(n.flavour != kPpoRllib ? k_ppo_adam<kPpoSb3> : log_stats ? k_ppo_adam<kPpoRllibLog> : k_ppo_adam<kPpoRllib>,
                        dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t ppo_launch_step_opt(const PpoNet& n, const PpoHp& hp, const PpoData& d, const PpoOpt& opt, const long long* idx,
+                               long long batch, float* m, float* v, long long* step_dev, float* scratch,
+                               const PpoScratch& s, float* stats7, hipStream_t st) {
+    float* grad = scratch + s.grad;
+    int32_t* stop = opt.target_kl > 0.0 ? opt.stop_dev : nullptr;
+    FbArgs f;
+    fb_args(f, n, hp, d, idx, batch, scratch, s);
+    const FbOpt fo{stop, opt.old_values, (float)opt.clip_range_vf};
+    hipLaunchKernelGGL(opt.clip_range_vf > 0.0 ? k_ppo_fb_opt<kFbSb3OptVf> : k_ppo_fb_opt<kFbSb3Opt>,
+                       dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f, fo);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    const GateArgs gate{stop, scratch + s.tile_stat, 1.5 * opt.target_kl};
+    DwArgs w;
+    const int wg = dw_args(w, f, n, hp, d, idx, batch, grad, scratch, s, step_dev);
+    hipLaunchKernelGGL(k_ppo_dw_opt, dim3((unsigned)wg), dim3(64 * kDwWaves), 0, st, w, gate);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    AdamArgs a;
+    adam_common(a, n, scratch, s, wg, batch, stats7);
+    a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
+    a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
+    a.update = 3;
+    const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
+    hipLaunchKernelGGL(k_ppo_adam_opt, dim3(grid), dim3(256), 0, st, a, gate);
     return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@ usage: tools/device_asm_kernels.py <this.s> <other.s> [regex]     (regex: only t
 
 Per kernel three pieces are compared: the body (from its label to its .Lfunc_end), its .amdhsa_kernel descriptor and
 its entry of the amdhsa.kernels metadata (arguments, register and LDS use).  The compilation-unit id
-(__hip_cuid_<hash>) and the function's index in its local labels are masked.  Prints one line per kernel; exits 1 if a compared kernel differs or the two files do not
+(__hip_cuid_<hash>) and the function's index in its local labels (with the padding behind such a label) are masked.  Prints one line per kernel; exits 1 if a compared kernel differs or the two files do not
 hold the same kernels.
 """
 import re
@@ -19,7 +19,9 @@ def kernels(path):
     # instantiation is added before it; the block numbers stay
     s = re.sub(r"BB\d+_(\d+)", r"BB_\1", s)
     s = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", s)
-    meta = re.split(r"^  - (?=\.agpr_count)", s.split("amdhsa.kernels:")[1], flags=re.M)
+    # a label's trailing comment is padded to a column, so the padding moves with the index's number of digits
+    s = re.sub(r"^(\.LBB_\d+:)[ \t]+;", r"\1 ;", s, flags=re.M)
+    meta = re.split(r"^  - (?=\.agpr_count)", s.split("amdhsa.kernels:")[1].split("amdhsa.target:")[0], flags=re.M)   # (not the file's trailer)
     out = {}
     for k in sorted(set(re.findall(r"^\s*\.amdhsa_kernel (\S+)", s, re.M))):
         q = re.escape(k)
