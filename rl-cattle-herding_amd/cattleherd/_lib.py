@@ -234,6 +234,12 @@ def lib():
         L.ch__mlp_kernel.restype = ctypes.c_char_p
         L.ch__mlp_plan.argtypes = [P(P(ChMlp)), P(i64), P(i32), i32, i32, i32, i32, i32, i32, P(i32 * 12)]
         L.ch__mlp_plan.restype = ctypes.c_int
+    if hasattr(L, "ch__ppo_plan"):   # internal: the PPO update's host-only step plan and kernel table, see ppo_plan below
+        L.ch__ppo_plan.argtypes = [i32, i32, i32, i32, i32, P(i32 * 6)]
+        L.ch__ppo_kernel.argtypes = [i32]
+        L.ch__ppo_kernel.restype = ctypes.c_char_p
+        L.ch__ppo_last_step.argtypes = [P(i32 * 5)]
+        L.ch__ppo_plan.restype = L.ch__ppo_last_step.restype = ctypes.c_int
     for pre, (N, H, D) in (("ch_ppo_", (P(ChPpoNet), P(ChPpoHparams), P(ChPpoData))),
                            ("ch_marl_ppo_", (P(ChMarlPpoNet), P(ChMarlPpoHparams), P(ChMarlPpoData)))):
         getattr(L, pre + "param_count").argtypes = [N]
@@ -338,6 +344,40 @@ def mlp_plan(nets, rows, cus, kcap=None, v1=False, nw4=False, wide4=False, rt=0)
     live = v[5]
     return {"v2": bool(v[0]), "rt": v[1], "lda": v[2], "ldh": v[3], "lds": v[4],
             "kernel": [MLP_KERNELS[k] for k in v[6:6 + live]], "grid": v[9:9 + live]}
+
+
+def ppo_kernel_table():
+    """Internal (tests / diagnostics): the names of the native PPO update's kernel table (csrc/ch_ppo.hip kPpoTable),
+    one per instantiation, row 0 "none"."""
+    rows = []
+    while True:
+        name = lib().ch__ppo_kernel(len(rows))
+        if name is None:
+            return rows
+        rows.append(name.decode())
+
+
+def ppo_plan(flavour, log=False, gate=False, vclip=False, opts=None):
+    """Internal (tests / diagnostics): what one minibatch step launches (csrc/ch_ppo.h ppo_plan; host only) for the
+    base ``flavour`` (0 SB3, 1 RLlib), ``*_train_log``'s statistics, and ``ch_ppo_train_opt`` with its KL gate armed
+    and / or its value clip on (``opts``: the call is ``ch_ppo_train_opt``; default: ``gate or vclip``).  Returns a
+    dict: the fb, dw and adam kernels' names, the update bits, the statistics row's width and whether the kernels take
+    the option structs.  Raises ``ChError`` for a combination that does not exist."""
+    out = (ctypes.c_int32 * 6)()
+    check(lib().ch__ppo_plan(flavour, int(log), int(gate or vclip if opts is None else opts), int(gate), int(vclip),
+                             ctypes.byref(out)))
+    names = ppo_kernel_table()
+    return {"fb": names[out[0]], "dw": names[out[1]], "adam": names[out[2]], "update": int(out[3]),
+            "n_stats": int(out[4]), "opts": bool(out[5])}
+
+
+def ppo_last_step():
+    """Internal (tests / diagnostics): the kernels of the PPO minibatch step launched last in this process, as
+    (fb, dw, adam names, the Adam launch's update bits, its grid) -- ch__ppo_last_step; kept on the host."""
+    out = (ctypes.c_int32 * 5)()
+    check(lib().ch__ppo_last_step(ctypes.byref(out)))
+    names = ppo_kernel_table()
+    return names[out[0]], names[out[1]], names[out[2]], int(out[3]), int(out[4])
 
 
 def default_config(mode, num_drones, num_cattle):

@@ -80,16 +80,16 @@ class NativeState:
         want = getattr(lib, self.fl.prefix + "scratch_size")(ctypes.byref(net), min(batch_size, n))
         if self.scratch is None or self.scratch.numel() < want:
             self.scratch = torch.empty(want, dtype=torch.float32, device=dev)
-        train = getattr(lib, self.fl.prefix + ("train_log" if log else "train"))
-        if opts is not None:
-            def train(net, hp, data, *rest, fn=lib.ch_ppo_train_opt, opts=ctypes.byref(opts)):
-                return fn(net, hp, data, opts, *rest)
+        # the entry point and what it takes ahead of the row indices
+        entry = "train_opt" if opts is not None else "train_log" if log else "train"
+        train = getattr(lib, self.fl.prefix + entry)
+        lead = [ctypes.byref(x) for x in (net, hp, data) + (() if opts is None else (opts,))]
         nb = (n + batch_size - 1) // batch_size
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             for e in range(n_epochs):
                 idx = draw()
-                _lib.check(train(ctypes.byref(net), ctypes.byref(hp), ctypes.byref(data), idx.data_ptr(), n, batch_size,
+                _lib.check(train(*lead, idx.data_ptr(), n, batch_size,
                                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(),
                                  None if stats is None else stats[e * nb].data_ptr(), self.scratch.data_ptr(), stream))
                 # (idx is freed to torch's caching allocator, which is stream-ordered: the launches read it first)

@@ -184,10 +184,11 @@ int grad(const typename F::Net* net, const typename F::Hparams* hp, const typena
     PpoScratch s;
     ppo_scratch_layout(n, batch, s);
     const PpoHp h = F::hp(hp);
+    const PpoPlan p = ppo_plan(F::kFlavour, false, false, false, false);   // ch_*_train's rows
     hipStream_t st = (hipStream_t)stream;
     int np = 0;
-    hipError_t e = ppo_launch_grad(n, h, d, reinterpret_cast<const long long*>(idx), batch, grad_flat, scratch, s, nullptr, &np, st);
-    if (e == hipSuccess) e = ppo_launch_stats(n, scratch, s, np, batch, stats, st);
+    hipError_t e = ppo_launch_grad(p, n, h, d, nullptr, reinterpret_cast<const long long*>(idx), batch, grad_flat, scratch, s, nullptr, &np, st);
+    if (e == hipSuccess) e = ppo_launch_stats(p, n, scratch, s, np, batch, stats, st);
     return e == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
 }
 
@@ -207,20 +208,33 @@ int adam(const typename F::Net* net, const typename F::Hparams* hp, const float*
     long long* step = reinterpret_cast<long long*>(step_dev);
     int np = 0;
     hipError_t e = ppo_launch_sumsq(n, grad_flat, scratch, s, step, &np, st);
-    if (e == hipSuccess) e = ppo_launch_adam(n, h, grad_flat, m, v, step, scratch, s, np, 1, nullptr, st);
+    if (e == hipSuccess)   // (ch_*_train's Adam row)
+        e = ppo_launch_adam(ppo_plan(F::kFlavour, false, false, false, false), n, &h, nullptr, grad_flat, m, v, step, scratch, s, np, 1, nullptr, st);
     return e == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
 }
 
-// log_stats: `stats` is required and wider -- Sb3 (ch_ppo_train_log): CH_PPO_LOG_STATS, with approx_kl and
-// clip_fraction; Rllib (ch_marl_ppo_train_log): CH_MARL_PPO_LOG_STATS, with vf_loss_unclipped, total_loss and
-// vf_explained_var
+// The three training entries.  kTrainLog: `stats` is required and wider -- Sb3 (ch_ppo_train_log): CH_PPO_LOG_STATS,
+// with approx_kl and clip_fraction; Rllib (ch_marl_ppo_train_log): CH_MARL_PPO_LOG_STATS, with vf_loss_unclipped,
+// total_loss and vf_explained_var.  kTrainOpt (ch_ppo_train_opt, Sb3 only): kTrainLog through the option kernels, with
+// `opts` and rows of CH_PPO_OPT_STATS.  ppo_plan has the kernels and the width of each.
+enum TrainKind { kTrain, kTrainLog, kTrainOpt };
+
 template <class F>
-int train(const typename F::Net* net, const typename F::Hparams* hp, const typename F::Data* data, const int64_t* idx,
-          int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
-          void* stream, bool log_stats = false) {
-    const std::string w = who<F>(log_stats ? "train_log" : "train");
-    if (!net || !hp || !data || !idx || !m || !v || !step_dev || !scratch || (log_stats && !stats))
+int train(TrainKind kind, const typename F::Net* net, const typename F::Hparams* hp, const typename F::Data* data,
+          const ch_ppo_opts* opts, const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v,
+          int64_t* step_dev, float* stats, float* scratch, void* stream) {
+    const std::string w = who<F>(kind == kTrainOpt ? "train_opt" : kind == kTrainLog ? "train_log" : "train");
+    if (!net || !hp || !data || !idx || !m || !v || !step_dev || !scratch || (kind != kTrain && !stats))
         return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
+    PpoOpt o{};
+    if (kind == kTrainOpt) {
+        if (!opts) return fail(nullptr, CH_ERR_INVALID, w + "NULL opts");
+        if (opts->clip_range_vf > 0.0 && !opts->old_values) return fail(nullptr, CH_ERR_INVALID, w + "clip_range_vf > 0 needs old_values");
+        if (opts->target_kl > 0.0 && !opts->stop_dev) return fail(nullptr, CH_ERR_INVALID, w + "target_kl > 0 needs stop_dev");
+        o = PpoOpt{opts->target_kl, opts->clip_range_vf, opts->old_values, opts->stop_dev};
+    }
+    const PpoPlan p = ppo_plan(F::kFlavour, kind == kTrainLog, kind == kTrainOpt, o.target_kl > 0.0, o.clip_range_vf > 0.0);
+    if (p.fb == kPpoNone) return fail(nullptr, CH_ERR_UNSUPPORTED, w + "no such update for this flavour");
     PpoNet n;
     PpoData d;
     std::string err;
@@ -234,53 +248,14 @@ int train(const typename F::Net* net, const typename F::Hparams* hp, const typen
     hipStream_t st = (hipStream_t)stream;
     float* grad = scratch + s.grad;
     long long* step = reinterpret_cast<long long*>(step_dev);
-    const int n_stats = !log_stats ? ppo_n_stats(F::kFlavour) : F::kFlavour == kPpoRllib ? CH_MARL_PPO_LOG_STATS : CH_PPO_LOG_STATS;
     int64_t k = 0;
     for (int64_t j = 0; j < n_idx; j += batch_size, ++k) {
         const int64_t batch = std::min(batch_size, n_idx - j);
-        PpoScratch sj = s;
-        sj.tiles = (int)((batch + kPpoTile - 1) / kPpoTile);
-        sj.bp = sj.tiles * kPpoTile;
+        const PpoScratch sj = ppo_scratch_for(s, batch);
         int np = 0;
-        hipError_t e = ppo_launch_grad(n, h, d, reinterpret_cast<const long long*>(idx) + j, batch, grad, scratch, sj, step, &np, st, log_stats);
+        hipError_t e = ppo_launch_grad(p, n, h, d, &o, reinterpret_cast<const long long*>(idx) + j, batch, grad, scratch, sj, step, &np, st);
         if (e == hipSuccess)
-            e = ppo_launch_adam(n, h, grad, m, v, step, scratch, sj, np, batch, stats ? stats + n_stats * k : nullptr, st, log_stats);
-        if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
-    }
-    return CH_OK;
-}
-
-// ch_ppo_train_opt (SB3 flavour only): train<Sb3> with log_stats, through the option kernels
-int train_opt(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const ch_ppo_opts* opts,
-              const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats,
-              float* scratch, void* stream) {
-    const std::string w = who<Sb3>("train_opt");
-    if (!net || !hp || !data || !idx || !m || !v || !step_dev || !scratch || !stats)
-        return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
-    if (!opts) return fail(nullptr, CH_ERR_INVALID, w + "NULL opts");
-    if (opts->clip_range_vf > 0.0 && !opts->old_values) return fail(nullptr, CH_ERR_INVALID, w + "clip_range_vf > 0 needs old_values");
-    if (opts->target_kl > 0.0 && !opts->stop_dev) return fail(nullptr, CH_ERR_INVALID, w + "target_kl > 0 needs stop_dev");
-    PpoNet n;
-    PpoData d;
-    std::string err;
-    int rc;
-    if ((rc = to_net<Sb3>(net, true, n, err)) || (rc = to_data<Sb3>(data, hp, d, err))) return fail(nullptr, rc, w + err);
-    if (n_idx < 1 || batch_size < 1 || batch_size > kMaxBatch) return fail(nullptr, CH_ERR_INVALID, w + "n_idx >= 1 and batch_size 1..2^24 required");
-    if (misaligned(scratch)) return fail(nullptr, CH_ERR_INVALID, w + "scratch must be 16-byte aligned");
-    PpoScratch s;
-    ppo_scratch_layout(n, std::min(batch_size, n_idx), s);
-    const PpoHp h = Sb3::hp(hp);
-    const PpoOpt o{opts->target_kl, opts->clip_range_vf, opts->old_values, opts->stop_dev};
-    hipStream_t st = (hipStream_t)stream;
-    long long* step = reinterpret_cast<long long*>(step_dev);
-    int64_t k = 0;
-    for (int64_t j = 0; j < n_idx; j += batch_size, ++k) {
-        const int64_t batch = std::min(batch_size, n_idx - j);
-        PpoScratch sj = s;
-        sj.tiles = (int)((batch + kPpoTile - 1) / kPpoTile);
-        sj.bp = sj.tiles * kPpoTile;
-        const hipError_t e = ppo_launch_step_opt(n, h, d, o, reinterpret_cast<const long long*>(idx) + j, batch, m, v, step,
-                                                 scratch, sj, stats + CH_PPO_OPT_STATS * k, st);
+            e = ppo_launch_adam(p, n, &h, &o, grad, m, v, step, scratch, sj, np, batch, stats ? stats + p.n_stats * k : nullptr, st);
         if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
     }
     return CH_OK;
@@ -306,19 +281,19 @@ int ch_ppo_adam(const ch_ppo_net* net, const ch_ppo_hparams* hp, const float* gr
 int ch_ppo_train(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
                  int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
                  void* stream) {
-    return train<Sb3>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
+    return train<Sb3>(kTrain, net, hp, data, nullptr, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
 }
 
 int ch_ppo_train_log(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const int64_t* idx,
                      int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev, float* stats, float* scratch,
                      void* stream) {
-    return train<Sb3>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream, true);
+    return train<Sb3>(kTrainLog, net, hp, data, nullptr, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
 }
 
 int ch_ppo_train_opt(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_ppo_data* data, const ch_ppo_opts* opts,
                      const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                      float* stats, float* scratch, void* stream) {
-    return train_opt(net, hp, data, opts, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
+    return train<Sb3>(kTrainOpt, net, hp, data, opts, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
 }
 
 int64_t ch_marl_ppo_param_count(const ch_marl_ppo_net* net) { return param_count<Rllib>(net); }
@@ -337,13 +312,37 @@ int ch_marl_ppo_adam(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, 
 int ch_marl_ppo_train(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
                       const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                       float* stats, float* scratch, void* stream) {
-    return train<Rllib>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
+    return train<Rllib>(kTrain, net, hp, data, nullptr, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
 }
 
 int ch_marl_ppo_train_log(const ch_marl_ppo_net* net, const ch_marl_ppo_hparams* hp, const ch_marl_ppo_data* data,
                           const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                           float* stats, float* scratch, void* stream) {
-    return train<Rllib>(net, hp, data, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream, true);
+    return train<Rllib>(kTrainLog, net, hp, data, nullptr, idx, n_idx, batch_size, m, v, step_dev, stats, scratch, stream);
+}
+
+// Internal (tests / diagnostics), host only: ppo_plan (ch_ppo.h) for a base flavour (0 SB3, 1 RLlib) and the four
+// switches -- the call has options, its KL gate is armed, its value clip is on -- as out = {fb, dw, adam rows of the
+// kernel table, update bits, statistics-row width, kernels take the option structs}; CH_ERR_UNSUPPORTED for a
+// combination that does not exist.
+int ch__ppo_plan(int32_t flavour, int32_t log_stats, int32_t opts, int32_t gate, int32_t vclip, int32_t out[6]) {
+    const PpoPlan p = ppo_plan(flavour, log_stats != 0, opts != 0, gate != 0, vclip != 0);
+    if (!out || p.fb == kPpoNone) return fail(nullptr, out ? CH_ERR_UNSUPPORTED : CH_ERR_INVALID, "ch__ppo_plan: no such update");
+    const int32_t v[6] = {p.fb, p.dw, p.adam, p.update, p.n_stats, p.opts};
+    std::copy(v, v + 6, out);
+    return CH_OK;
+}
+
+// Internal: row `kernel` of the update's kernel table (ch_ppo.hip kPpoTable), its name; NULL past the table.
+const char* ch__ppo_kernel(int32_t kernel) { return ppo_kernel_name(kernel); }
+
+// Internal: the minibatch step launched last in this process (host record, no device work): out = {fb, dw, adam rows,
+// the Adam launch's update bits, its grid}.  ch_*_adam leaves {0, k_ppo_sumsq's row, ...}.
+int ch__ppo_last_step(int32_t out[5]) {
+    if (!out) return CH_ERR_INVALID;
+    const int32_t v[5] = {g_ppo_last_step.fb, g_ppo_last_step.dw, g_ppo_last_step.adam, g_ppo_last_step.update, g_ppo_last_step.adam_grid};
+    std::copy(v, v + 5, out);
+    return CH_OK;
 }
 
 }  // extern "C"

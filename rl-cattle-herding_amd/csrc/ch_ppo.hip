@@ -15,19 +15,22 @@
 //               torch's Adam on its slice.  The step count was incremented by k_ppo_dw, so the loop over minibatches
 //               is stream-ordered with no host sync.
 //
-// The three kernels take a compile-time flavour (ch_ppo.h).  kPpoRllib is the minibatch step of RLlib's PPO learner for
-// the DTDE driver's shared policy (cattleherd/marl_ppo.py restates it): the head is [mean, raw log_std], the loss adds
-// the KL penalty against the gathered old dist inputs and clips the value error, k_ppo_dw has no log_std workgroup and
-// k_ppo_adam a no-clip mode and five statistics.  kPpoSb3 is the step described above; for
-// ch_ppo_train_log a third k_ppo_fb instantiation (kFbSb3Log) also leaves per-tile sums of SB3's two diagnostics
-// (approx_kl, clip_fraction), which k_ppo_adam turns into two more statistics.  For
-// ch_marl_ppo_train_log a fourth flavour (kPpoRllibLog) of k_ppo_fb and k_ppo_adam adds RLlib's vf_loss_unclipped,
-// total_loss and vf_explained_var.
+// The kernels take a compile-time flavour F (ch_ppo.h lists the six and what each adds to its base).  The three bodies
+// live in ch_ppo_{fb,dw,adam}_body.inc, included into the plain kernels and into ch_ppo_train_opt's (*_opt, which take
+// an option struct behind the plain arguments: DESIGN.md 4.11, Options).  The 14 instantiations, one row of kPpoTable
+// each; ppo_plan (ch_ppo.h) picks the rows an ABI entry launches:
 //
-// ch_ppo_train_opt (SB3's target_kl and clip_range_vf) has kernels of its own -- k_ppo_fb_opt, k_ppo_dw_opt,
-// k_ppo_adam_opt -- over the same three bodies, which live in ch_ppo_{fb,dw,adam}_body.inc and are included into the
-// plain and the option kernels alike (Options): the stop word's early return, the clipped value
-// prediction, and the KL gate that every workgroup decides for itself from the same scratch sums.
+//   kernel          | kPpoSb3 0 | kPpoRllib 1 | kFbSb3Log 2 | kPpoRllibLog 3 | kFbSb3Opt 4 | kFbSb3OptVf 5
+//   k_ppo_fb        |     x     |      x      |      x      |       x        |             |
+//   k_ppo_fb_opt    |           |             |             |                |      x      |       x
+//   k_ppo_dw        |     x     |      x      |             |                |             |
+//   k_ppo_dw_opt    |  x + gate |             |             |                |             |
+//   k_ppo_adam      |     x     |      x      |             |       x        |             |
+//   k_ppo_adam_opt  |  x + gate |             |             |                |             |
+//   k_ppo_sumsq     no flavour: ch_ppo_adam's sum of squares of a given gradient
+//
+// (k_ppo_dw is the same for a base and its log flavour; k_ppo_adam<kPpoSb3> writes kFbSb3Log's two statistics under a
+// run-time bit of AdamArgs::update.  DESIGN.md 4.12 - 4.14 describe the flavours.)
 //
 // MFMA operand map (16x16x4 f32): lane l gives A[row l & 15][k slot l >> 4] and B[k slot l >> 4][col l & 15]; it
 // holds C/D[row 4 (l >> 4) + r][col l & 15] in register r.  Which k a slot stands for is free as long as A and B
@@ -156,23 +159,6 @@ struct FbArgs {
     float ent_coef, vf_clip, ls_clip;
     const float* kl_coeff_dev;
 };
-
-// k_ppo_fb's third flavour (ch_ppo_train_log): kPpoSb3 plus the per-tile sums of SB3's two diagnostics.  A kernel of
-// its own, so that ch_ppo_train's carries none of the float64 code.
-constexpr int kFbSb3Log = 2;
-// the fourth, of k_ppo_fb and of the Adam kernel (ch_marl_ppo_train_log): kPpoRllib plus what RLlib's learner record
-// lacks in the five statistics -- the critic workgroups leave the loss's coefficients, each tile's sum of unclipped
-// squared value errors and each row's (value, target) in the scratch region `misc` (unused by kPpoRllib otherwise:
-// [4] coefficients, [tiles] sums, [bp][2] rows), and k_ppo_adam turns them into vf_loss_unclipped, total_loss and
-// vf_explained_var.
-// Kernels of their own, so that ch_marl_ppo_train launches what it launched before.
-constexpr int kPpoRllibLog = 3;
-constexpr bool ppo_rllib(int F) { return F == kPpoRllib || F == kPpoRllibLog; }
-// the fifth and sixth, of k_ppo_fb (ch_ppo_train_opt): kFbSb3Log behind the stop word's early return, and that with
-// SB3's clip_range_vf.  Kernels of their own again (k_ppo_fb_opt): the four above stay the code they were.
-constexpr int kFbSb3Opt = 4;
-constexpr int kFbSb3OptVf = 5;
-constexpr bool fb_opt(int F) { return F == kFbSb3Opt || F == kFbSb3OptVf; }
 
 // What ch_ppo_train_opt's kernels take beside the arguments of the plain ones.  NoOpt: the plain
 // kernels, whose bodies compile to what they were.
@@ -402,12 +388,35 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 constexpr int kSumsqGrid = 128;
 
+// The kernel table, by PpoKernel: an instantiation's name (cattleherd/_lib.py ppo_kernel_table), its host handle and
+// its workgroup size.
+struct PpoKernelRow { const char* name; const void* fn; unsigned block; };
+#define CH_ROW(KERNEL, BLOCK) {#KERNEL, reinterpret_cast<const void*>(&KERNEL), BLOCK}
+const PpoKernelRow kPpoTable[kPpoKernels] = {   // in PpoKernel's order
+    {"none", nullptr, 0},
+    CH_ROW(k_ppo_fb<0>, 64 * kFbWaves), CH_ROW(k_ppo_fb<1>, 64 * kFbWaves), CH_ROW(k_ppo_fb<2>, 64 * kFbWaves),
+    CH_ROW(k_ppo_fb<3>, 64 * kFbWaves), CH_ROW(k_ppo_fb_opt<4>, 64 * kFbWaves), CH_ROW(k_ppo_fb_opt<5>, 64 * kFbWaves),
+    CH_ROW(k_ppo_dw<0>, 64 * kDwWaves), CH_ROW(k_ppo_dw<1>, 64 * kDwWaves), CH_ROW(k_ppo_dw_opt, 64 * kDwWaves),
+    CH_ROW(k_ppo_sumsq, 256),
+    CH_ROW(k_ppo_adam<0>, 256), CH_ROW(k_ppo_adam<1>, 256), CH_ROW(k_ppo_adam<3>, 256), CH_ROW(k_ppo_adam_opt, 256),
+};
+#undef CH_ROW
+
+// launches row `k` over the kernel's arguments (an option kernel's struct last: a plain kernel does not read it)
+hipError_t launch(int k, dim3 grid, void** args, hipStream_t st) {
+    (void)hipLaunchKernel(kPpoTable[k].fn, grid, dim3(kPpoTable[k].block), args, 0, st);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+PpoLastStep g_ppo_last_step = {kPpoNone, kPpoNone, kPpoNone, 0, 0};
+
+const char* ppo_kernel_name(int row) { return row >= 0 && row < kPpoKernels ? kPpoTable[row].name : nullptr; }
 
 void ppo_scratch_layout(const PpoNet& n, long long batch, PpoScratch& s) {
     std::memset(&s, 0, sizeof(s));
-    s.tiles = (int)((batch + kPpoTile - 1) / kPpoTile);
-    s.bp = s.tiles * kPpoTile;
+    s = ppo_scratch_for(s, batch);
     long long o = 0;
     auto take = [&](long long floats) { const long long at = o; o += (floats + 3) / 4 * 4; return at; };   // 16-byte steps
     for (int ni = 0; ni < 2; ++ni) {
@@ -467,36 +476,47 @@ int dw_args(DwArgs& w, const FbArgs& f, const PpoNet& n, const PpoHp& hp, const 
     return wg;
 }
 
+// the gate as ch_ppo_train_opt's weight-gradient and Adam kernels take it (a plain kernel's plan: no options, unused)
+GateArgs gate_args(const PpoPlan& p, const PpoOpt* opt, float* scratch, const PpoScratch& s) {
+    return p.opts ? GateArgs{ppo_stop(*opt), scratch + s.tile_stat, 1.5 * opt->target_kl} : GateArgs{};
+}
+
 }  // namespace
 
-hipError_t ppo_launch_grad(const PpoNet& n, const PpoHp& hp, const PpoData& d, const long long* idx, long long batch,
-                           float* grad, float* scratch, const PpoScratch& s, long long* step_dev, int* n_partials,
-                           hipStream_t st, bool log_stats) {
+hipError_t ppo_launch_grad(const PpoPlan& p, const PpoNet& n, const PpoHp& hp, const PpoData& d, const PpoOpt* opt,
+                           const long long* idx, long long batch, float* grad, float* scratch, const PpoScratch& s,
+                           long long* step_dev, int* n_partials, hipStream_t st) {
     FbArgs f;
     fb_args(f, n, hp, d, idx, batch, scratch, s);
-    const bool rllib = n.flavour == kPpoRllib;
-    hipLaunchKernelGGL(rllib ? (log_stats ? k_ppo_fb<kPpoRllibLog> : k_ppo_fb<kPpoRllib>)
-                             : (log_stats ? k_ppo_fb<kFbSb3Log> : k_ppo_fb<kPpoSb3>),
-                       dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f);
-    hipError_t e = hipGetLastError();
+    FbOpt fo = p.opts ? FbOpt{ppo_stop(*opt), opt->old_values, (float)opt->clip_range_vf} : FbOpt{};
+    void* fb[] = {&f, &fo};
+    g_ppo_last_step.fb = p.fb; g_ppo_last_step.dw = p.dw;
+    hipError_t e = launch(p.fb, dim3((unsigned)s.tiles, 2), fb, st);
     if (e != hipSuccess) return e;
 
+    GateArgs gate = gate_args(p, opt, scratch, s);
     DwArgs w;
     const int wg = dw_args(w, f, n, hp, d, idx, batch, grad, scratch, s, step_dev);
-    hipLaunchKernelGGL(rllib ? k_ppo_dw<kPpoRllib> : k_ppo_dw<kPpoSb3>, dim3((unsigned)wg), dim3(64 * kDwWaves), 0, st, w);
+    void* dw[] = {&w, &gate};
     *n_partials = wg;
-    return hipGetLastError();
+    return launch(p.dw, dim3((unsigned)wg), dw, st);
 }
 
 hipError_t ppo_launch_sumsq(const PpoNet& n, const float* grad, float* scratch, const PpoScratch& s, long long* step_dev,
                             int* n_partials, hipStream_t st) {
-    hipLaunchKernelGGL(k_ppo_sumsq, dim3(kSumsqGrid), dim3(256), 0, st, grad, n.n_params, scratch + s.partial, step_dev);
+    long long count = n.n_params;
+    float* partial = scratch + s.partial;
+    void* args[] = {&grad, &count, &partial, &step_dev};
+    g_ppo_last_step.fb = kPpoNone; g_ppo_last_step.dw = kPpoSumsq;
     *n_partials = kSumsqGrid;
-    return hipGetLastError();
+    return launch(kPpoSumsq, dim3(kSumsqGrid), args, st);
 }
 
-static void adam_common(AdamArgs& a, const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                        float* stats) {
+// `hp` NULL: the statistics alone, by one workgroup (ppo_launch_stats)
+hipError_t ppo_launch_adam(const PpoPlan& p, const PpoNet& n, const PpoHp* hp, const PpoOpt* opt, const float* grad,
+                           float* m, float* v, const long long* step_dev, float* scratch, const PpoScratch& s,
+                           int n_partials, long long batch, float* stats, hipStream_t st) {
+    AdamArgs a;
     std::memset(&a, 0, sizeof(a));
     for (int ni = 0; ni < 2; ++ni) {
         const PpoMlp& m = n.net[ni];
@@ -511,58 +531,17 @@ static void adam_common(AdamArgs& a, const PpoNet& n, float* scratch, const PpoS
     a.n_params = n.n_params;
     a.partial = scratch + s.partial; a.n_partials = n_partials;
     a.stats4 = stats; a.tile_stat = scratch + s.tile_stat; a.misc = scratch + s.misc; a.tiles = s.tiles; a.batch = batch;
-}
-
-hipError_t ppo_launch_adam(const PpoNet& n, const PpoHp& hp, const float* grad, float* m, float* v,
-                           const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                           float* stats, hipStream_t st, bool log_stats) {
-    AdamArgs a;
-    adam_common(a, n, scratch, s, n_partials, batch, stats);
-    a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
-    a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
-    a.update = log_stats ? 3 : 1;
-    const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
-    hipLaunchKernelGGL(n.flavour != kPpoRllib ? k_ppo_adam<kPpoSb3> : log_stats ? k_ppo_adam<kPpoRllibLog> : k_ppo_adam<kPpoRllib>,
-                       dim3(grid), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t ppo_launch_step_opt(const PpoNet& n, const PpoHp& hp, const PpoData& d, const PpoOpt& opt, const long long* idx,
-                               long long batch, float* m, float* v, long long* step_dev, float* scratch,
-                               const PpoScratch& s, float* stats7, hipStream_t st) {
-    float* grad = scratch + s.grad;
-    int32_t* stop = opt.target_kl > 0.0 ? opt.stop_dev : nullptr;
-    FbArgs f;
-    fb_args(f, n, hp, d, idx, batch, scratch, s);
-    const FbOpt fo{stop, opt.old_values, (float)opt.clip_range_vf};
-    hipLaunchKernelGGL(opt.clip_range_vf > 0.0 ? k_ppo_fb_opt<kFbSb3OptVf> : k_ppo_fb_opt<kFbSb3Opt>,
-                       dim3((unsigned)s.tiles, 2), dim3(64 * kFbWaves), 0, st, f, fo);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-
-    const GateArgs gate{stop, scratch + s.tile_stat, 1.5 * opt.target_kl};
-    DwArgs w;
-    const int wg = dw_args(w, f, n, hp, d, idx, batch, grad, scratch, s, step_dev);
-    hipLaunchKernelGGL(k_ppo_dw_opt, dim3((unsigned)wg), dim3(64 * kDwWaves), 0, st, w, gate);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-
-    AdamArgs a;
-    adam_common(a, n, scratch, s, wg, batch, stats7);
-    a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
-    a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.max_grad_norm = hp.max_grad_norm;
-    a.update = 3;
-    const unsigned grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
-    hipLaunchKernelGGL(k_ppo_adam_opt, dim3(grid), dim3(256), 0, st, a, gate);
-    return hipGetLastError();
-}
-
-hipError_t ppo_launch_stats(const PpoNet& n, float* scratch, const PpoScratch& s, int n_partials, long long batch,
-                            float* stats, hipStream_t st) {
-    AdamArgs a;
-    adam_common(a, n, scratch, s, n_partials, batch, stats);
-    hipLaunchKernelGGL(n.flavour == kPpoRllib ? k_ppo_adam<kPpoRllib> : k_ppo_adam<kPpoSb3>, dim3(1), dim3(256), 0, st, a);
-    return hipGetLastError();
+    unsigned grid = 1;
+    if (hp) {
+        a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
+        a.lr = hp->lr; a.beta1 = hp->beta1; a.beta2 = hp->beta2; a.eps = hp->eps; a.max_grad_norm = hp->max_grad_norm;
+        a.update = p.update;
+        grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
+    }
+    GateArgs gate = gate_args(p, opt, scratch, s);
+    void* args[] = {&a, &gate};
+    g_ppo_last_step.adam = p.adam; g_ppo_last_step.update = a.update; g_ppo_last_step.adam_grid = (int)grid;
+    return launch(p.adam, dim3(grid), args, st);
 }
 
 }  // namespace ch
