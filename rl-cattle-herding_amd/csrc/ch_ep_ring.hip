@@ -8,65 +8,34 @@
 
 #include <algorithm>
 
+#include "ch_episode_dev.h"
 #include "ch_internal.h"
 
 namespace ch {
 
 // ---- the episode ring ------------------------------------------------------------------------------------------
 // One workgroup.  C, the number of envs that ended in the step, decides who writes (only the last W of the step), so
-// the envs are walked twice: a counting pass, then the ranking pass of k_stage_ended (ch_aux.hip) -- each chunk of
-// 1024 envs ranked by wave ballots and a scan of the 16 wave totals, so that the ranks follow the env order.  Episode
-// total + r goes to slot (total + r) % W; with r >= C - W every slot has exactly one writer: plain stores.
-constexpr int kRingThreads = 1024;
-constexpr int kRingWaves = kRingThreads / 64;
-
-__global__ __launch_bounds__(kRingThreads) void k_ep_ring_record(EpRingArgs a) {
-    __shared__ long long wsum[kRingWaves + 1];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+// the envs are walked twice: count_ended, then ranked_walk in ascending env order; the slot is ring_slot's
+// (ch_episode_dev.h for all three).
+__global__ __launch_bounds__(kEpisodeThreads) void k_ep_ring_record(EpRingArgs a) {
+    __shared__ long long wsum[kEpisodeWaves + 1];
     const long long total = *a.total;   // (rewritten by thread 0 at the very end, behind the barriers below)
-    // the counting pass: each wave's count over its lanes' envs, then the waves in index order
-    long long mine = 0;
-    for (long long c0 = 0; c0 < a.E; c0 += kRingThreads) {
-        const long long e = c0 + t;
-        mine += __popcll(__ballot(e < a.E && a.reset[e] != 0));   // (the same in every lane of the wave)
-    }
-    if (lane == 0) wsum[w] = mine;
-    __syncthreads();
-    long long C = 0;
-    for (int k = 0; k < kRingWaves; ++k) C += wsum[k];
-    __syncthreads();
+    const long long C = count_ended(a.E, a.reset, wsum);
     if (C == 0) return;   // (uniform: most steps end no episode)
     const long long first = C > a.W ? C - a.W : 0;   // ranks below it would be overwritten within this step
-    long long base = 0;
-    for (long long c0 = 0; c0 < a.E; c0 += kRingThreads) {
-        const long long e = c0 + t;
-        const bool f = e < a.E && a.reset[e] != 0;
-        const unsigned long long m = __ballot(f);
-        if (lane == 0) wsum[w] = __popcll(m);
-        __syncthreads();
-        if (t == 0) {
-            long long s = 0;
-            for (int k = 0; k < kRingWaves; ++k) { const long long v = wsum[k]; wsum[k] = s; s += v; }
-            wsum[kRingWaves] = s;
+    ranked_walk(a.E, a.reset, wsum, [&](long long e, long long r) {
+        if (r >= first) {
+            const long long slot = ring_slot(total, r, a.W);
+            a.ep_return[slot] = a.stats[2 * e];
+            a.ep_length[slot] = (int)a.stats[2 * e + 1];
+            a.ep_env[slot] = (int)e;
         }
-        __syncthreads();
-        if (f) {
-            const long long r = base + wsum[w] + __popcll(m & ((1ull << lane) - 1ull));
-            if (r >= first) {
-                const long long slot = (total + r) % a.W;   // 0 <= slot < W
-                a.ep_return[slot] = a.stats[2 * e];
-                a.ep_length[slot] = (int)a.stats[2 * e + 1];
-                a.ep_env[slot] = (int)e;
-            }
-        }
-        base += wsum[kRingWaves];
-        __syncthreads();
-    }
-    if (t == 0) *a.total = total + C;
+    });
+    if (threadIdx.x == 0) *a.total = total + C;
 }
 
 hipError_t launch_ep_ring_record(const EpRingArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(k_ep_ring_record, dim3(1), dim3(kRingThreads), 0, st, a);
+    hipLaunchKernelGGL(k_ep_ring_record, dim3(1), dim3(kEpisodeThreads), 0, st, a);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 // recorder runs after each ch_step on the step's reset_happened / episode_stats.
 #include <hip/hip_runtime.h>
 
+#include "ch_episode_dev.h"
 #include "ch_internal.h"
 
 namespace ch {
@@ -20,13 +21,12 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_begin(EvalArgs a, long lo
     const long long e = (long long)blockIdx.x * kEvalThreads + threadIdx.x;
     if (e == 0) *a.remaining = n_eval;
     if (e >= a.E) return;
-    a.quota[e] = (int)((n_eval + e) / a.E);
+    a.quota[e] = eval_quota(e, n_eval, a.E);
     a.count[e] = 0;
 }
 
-// one thread per env (coalesced reads of the step's outputs).  `remaining` drops by the wave's number of recorded
-// episodes in one integer atomic per wave (ballot + popcount): integer adds commute, so the result does not depend on
-// the order the waves arrive in.  The slot is below the capacity whatever the quota array holds.
+// one thread per env (coalesced reads of the step's outputs).  The slot is below the capacity whatever the quota array
+// holds; `remaining` drops as ch_episode_dev.h drop_remaining says.
 __device__ __forceinline__ void eval_record_env(const EvalArgs& a, long long e) {
     bool rec = false;
     if (e < a.E && a.reset[e] != 0) {
@@ -41,9 +41,7 @@ __device__ __forceinline__ void eval_record_env(const EvalArgs& a, long long e) 
             a.count[e] = c + 1;
         }
     }
-    const unsigned long long m = __ballot(rec);   // (every lane of the wave gets here)
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.remaining), 0ull - (unsigned long long)__popcll(m));
+    drop_remaining(a.remaining, rec);   // (every lane of the wave gets here)
 }
 
 __global__ __launch_bounds__(kEvalThreads) void k_eval_record(EvalArgs a) {

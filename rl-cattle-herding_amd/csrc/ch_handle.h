@@ -1,8 +1,7 @@
 // ch_handle.h — the handle behind the C ABI, private to its host files: ch_api.cpp (config, create / destroy, reset,
 // step, state, metrics, host output), ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection),
-// ch_api_eval.cpp (the on-device evaluate_policy), ch_api_marl_eval.cpp (the DTDE driver's evaluation),
-// ch_api_eval_log.cpp (the device-side evaluator log), ch_api_train_log.cpp (the SB3 training log) and
-// ch_api_marl_train_log.cpp (the RLlib training log).
+// ch_api_eval.cpp (the on-device evaluate_policy and the DTDE driver's evaluation), ch_api_eval_log.cpp (the device-side
+// evaluator log) and ch_api_train_log.cpp (the SB3 and the RLlib training log).
 #pragma once
 #include <string>
 #include <vector>
@@ -120,7 +119,7 @@ int device_status(ch_handle* h, int word);
 // ring, a CTDE handle, and -- with `io` -- a step io that carries reset_happened and episode_stats; fills `a`
 int ep_ring_args(ch_handle* h, const ch_ep_ring* ring, const ch_step_io* io, ch::EpRingArgs& a, const char* who);
 
-// the MARL episode ring's checks (ch_api_marl_train_log.cpp; ch_marl_ep_ring_record and ch_marl_rollout_collect_log
+// the MARL episode ring's checks (ch_api_train_log.cpp; ch_marl_ep_ring_record and ch_marl_rollout_collect_log
 // share them): a whole ring, a MARL handle under the wrapper's semantics, and -- with `io` -- a step io that carries
 // reward and reset_happened; fills `a` but for `live`
 int marl_ring_args(ch_handle* h, const ch_marl_ep_ring* ring, const ch_step_io* io, ch::MarlRingArgs& a, const char* who);

@@ -209,7 +209,7 @@ struct RolloutArgs {
     float *env_actions, *obs, *actions, *rewards, *episode_starts, *values, *log_probs, *advantages, *returns,
         *last_episode_starts;
 };
-hipError_t launch_rollout(const RolloutArgs& a, int which, hipStream_t st);
+hipError_t launch_rollout(const RolloutArgs& a, int which, hipStream_t st);   // 0 store, 1 post, 2 gae, 3 apply (cap slots)
 // ch_aux.hip: the DTDE (RLlib) per-agent rollout (ch_marl_rollout_collect); rows = E * N agents
 struct MarlArgs {
     int T, t, A, N;
@@ -232,7 +232,7 @@ hipError_t launch_marl_rollout(const MarlArgs& a, int which, hipStream_t st);   
 // ch_aux.hip: ch_outputs_to_host's compaction of the envs that auto-reset (ascending env order)
 hipError_t launch_stage_ended(long long E, const uint8_t* reset, const float* term_obs, const double* stats,
                               int blk_floats, long long* count, long long* env_out, double* stats_out, float* obs_out,
-                              hipStream_t st);   // 0 store, 1 post, 2 gae, 3 apply (cap slots)
+                              hipStream_t st);
 
 // ch_eval.hip: the on-device evaluate_policy (ch_eval_*): the episode table's begin and recorder kernels and the
 // deterministic-action kernel of ch_evaluate_policy

@@ -10,10 +10,10 @@
 // The quota rule and `remaining` are the CTDE table's (ch_eval.hip): quota[e] = (n + e) / E, slot = the env's count.
 // What the CTDE table takes from the step's episode_stats is kept here per agent: `live` (marked before the step: the
 // wrapper's self.agents, k_marl_store's mask), and the accumulators acc_return / acc_length / acc_steps the recorder
-// advances after it.  One thread per env loops its N <= 12 agents in index order, so every float64 sum has one fixed
-// order and the same inputs give the same bits.
+// advances after it (ch_episode_dev.h: one thread per env, its N <= 12 agents in index order).
 #include <hip/hip_runtime.h>
 
+#include "ch_episode_dev.h"
 #include "ch_internal.h"
 
 namespace ch {
@@ -24,18 +24,14 @@ __global__ __launch_bounds__(kMarlEvalThreads) void k_marl_eval_begin(MarlEvalAr
     const long long e = (long long)blockIdx.x * kMarlEvalThreads + threadIdx.x;
     if (e == 0) *a.remaining = n_eval;
     if (e >= a.E) return;
-    a.quota[e] = (int)((n_eval + e) / a.E);
+    a.quota[e] = eval_quota(e, n_eval, a.E);
     a.count[e] = 0;
     a.acc_steps[e] = 0;
-    for (int i = 0; i < a.N; ++i) {
-        a.acc_return[e * a.N + i] = 0.0;
-        a.acc_length[e * a.N + i] = 0;
-    }
+    episode_zero(e, a.N, a.acc_return, a.acc_length);
 }
 
-// the wrapper's self.agents at the start of a step: agent i < NUM_DRONES and not dropped out (k_marl_store's `live`)
 __device__ __forceinline__ bool marl_eval_live(const MarlEvalArgs& a, long long e, int i) {
-    return i < a.env_n[e] && ((a.env_active[e] >> i) & 1);
+    return agent_live(a.env_n, a.env_active, e, i);
 }
 
 __device__ __forceinline__ void marl_eval_mark_env(const MarlEvalArgs& a, long long e) {
@@ -44,48 +40,27 @@ __device__ __forceinline__ void marl_eval_mark_env(const MarlEvalArgs& a, long l
 }
 
 // one thread per env: the step's rewards of the agents marked live into the accumulators, then, where the env ended,
-// the episode into slot count[e] (below the capacity whatever the quota array holds) and the accumulators back to 0.
-// `remaining` drops by the wave's number of filed episodes in one integer atomic per wave (ballot + popcount), as in
-// ch_eval.hip: integer adds commute, so the result does not depend on the order the waves arrive in.
+// the episode into slot count[e] (below the capacity whatever the quota array holds) and the accumulators back to 0
+// (ch_episode_dev.h for each piece, and for how `remaining` drops).
 __device__ __forceinline__ void marl_eval_record_env(const MarlEvalArgs& a, long long e) {
     bool rec = false;
     if (e < a.E) {
-        const long long r0 = e * a.N;
-        for (int i = 0; i < a.N; ++i) {
-            if (a.live[r0 + i]) {
-                a.acc_return[r0 + i] += (double)a.reward[r0 + i];
-                a.acc_length[r0 + i] += 1;
-            }
-        }
-        const int steps = a.acc_steps[e] + 1;
-        a.acc_steps[e] = steps;
+        const int steps = episode_accumulate(e, a.N, a.live, a.reward, a.acc_return, a.acc_length, a.acc_steps);
         if (a.reset[e] != 0) {
             const int c = a.count[e];
             if (c < a.quota[e] && c < a.C) {
                 rec = true;
                 const long long s = e * a.C + c;
-                double sum = 0.0;
-                for (int i = 0; i < a.N; ++i) {
-                    const double r = a.acc_return[r0 + i];
-                    a.agent_return[s * a.N + i] = r;
-                    a.agent_length[s * a.N + i] = a.acc_length[r0 + i];
-                    sum += r;
-                }
-                a.ep_return[s] = sum;
+                a.ep_return[s] = episode_file(e, a.N, a.acc_return, a.acc_length, s, a.agent_return, a.agent_length);
                 a.ep_length[s] = steps;
                 a.ep_end_step[s] = a.step_index;
                 a.count[e] = c + 1;
             }
-            for (int i = 0; i < a.N; ++i) {
-                a.acc_return[r0 + i] = 0.0;
-                a.acc_length[r0 + i] = 0;
-            }
+            episode_zero(e, a.N, a.acc_return, a.acc_length);
             a.acc_steps[e] = 0;
         }
     }
-    const unsigned long long m = __ballot(rec);   // (every lane of the wave gets here)
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.remaining), 0ull - (unsigned long long)__popcll(m));
+    drop_remaining(a.remaining, rec);   // (every lane of the wave gets here)
 }
 
 __global__ __launch_bounds__(kMarlEvalThreads) void k_marl_eval_mark(MarlEvalArgs a) {
