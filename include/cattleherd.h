@@ -401,6 +401,89 @@ int ch_rollout_collect_log(ch_handle* h, const ch_rollout* rb, const ch_rollout_
                            const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
                            int32_t bootstrap_truncated, const ch_ep_ring* ring, void* stream);
 
+/* ---- Device-side VecNormalize: running observation / return statistics for the CTDE PPO path -----------------
+ * Replaces: stable_baselines3 VecNormalize(venv, training, norm_obs, norm_reward, clip_obs, clip_reward, gamma,
+ * epsilon) around the reference's VecEnv, and its two RunningMeanStd (obs_rms over the observation features, ret_rms
+ * over the envs' discounted returns): update(x[n]) merges the batch mean, population variance and n into the running
+ * (mean, var, count) by update_from_moments; the initial state is mean 0, var 1, count 1e-4.  All statistics are
+ * float64.  (SB3 is not installed here: restated from its source, "parity unpinned".)  Not restated: norm_obs_keys /
+ * dict observations, SB3's pickled file, MARL handles (RLlib normalises with connectors).
+ * The struct lives in host memory and is read at each call; every array is caller-owned DEVICE memory.  The five
+ * statistic arrays are meant to be views of one block (mean, var, count, ret_stats, ret), so that a checkpoint is one
+ * copy each way.  All work is enqueued on `stream`, with no host synchronisation; one stream per normaliser.
+ * Determinism: no floating-point atomics; every sum has a fixed order, so the same state and input give the same bits.
+ * Failures of the handle-free entry points are reported by ch_last_error(NULL). */
+typedef struct ch_norm {
+    int32_t dim;               /* observation features (a CTDE handle's obs_rows * 86) */
+    int32_t training;          /* non-zero: the statistics move (VecNormalize.training) */
+    int32_t norm_obs;          /* non-zero: observations are normalised; 0: ch_norm_obs_apply copies */
+    int32_t norm_reward;       /* non-zero: rewards are normalised; 0: ch_norm_reward copies them (ret_rms still moves) */
+    double clip_obs;           /* >= 0 (10) */
+    double clip_reward;        /* >= 0 (10) */
+    double epsilon;            /* >= 0 (1e-8) */
+    double gamma;              /* the return's discount (0.99) */
+    int64_t n_envs;            /* E: rows of ret */
+    double* mean;              /* device [dim]  obs_rms.mean */
+    double* var;               /* device [dim]  obs_rms.var */
+    double* count;             /* device [1]    obs_rms.count */
+    double* ret_stats;         /* device [3]    ret_rms.mean, .var, .count */
+    double* ret;               /* device [E]    VecNormalize.returns */
+    double* scratch;           /* device [scratch_doubles]: the reductions' partials (contents not kept) */
+    int64_t scratch_doubles;   /* >= ch_norm_scratch_size(rows, dim) of every matrix passed, and of (E, dim) */
+    float* obs_n;              /* ch_rollout_collect_norm only (NULL otherwise): device [E][dim], the normalised observation */
+    float* terminal_obs_n;     /*   device [E][dim]: the normalised terminal observations of the envs that reset */
+    float* reward_n;           /*   device [E]: the normalised reward */
+} ch_norm;
+
+/* Doubles of scratch ch_norm_obs_update takes for a [rows][dim] matrix (and ch_norm_reward for `rows` envs); -1 for
+ * rows or dim outside [1, 2^24].  Host only. */
+int64_t ch_norm_scratch_size(int64_t rows, int32_t dim);
+
+/* Replaces: RunningMeanStd.__init__ for both statistics and VecNormalize's returns = zeros: mean 0, var 1, count 1e-4,
+ * ret 0, on `stream`. */
+int ch_norm_begin(const ch_norm* norm, void* stream);
+
+/* Replaces: obs_rms.update(x) for a device float32 [rows][dim] matrix (no handle: any matrix will do).  A no-op
+ * unless training and norm_obs.  Two launches: the batch moments per (column tile, row chunk) workgroup -- float4 loads
+ * along dim where dim % 4 == 0 and x is 16-byte aligned, a scalar path otherwise; two-pass variance over 64 rows held
+ * in registers, Chan's merge above, all of x - x[0][column] -- and the merge of the chunks in index order with the
+ * running update, the only writer of mean / var / count (a launch of its own: no workgroup reads the running statistics
+ * while another writes them). */
+int ch_norm_obs_update(const ch_norm* norm, const float* x, int64_t rows, void* stream);
+
+/* Replaces: VecNormalize.normalize_obs: y = float32(clip((float64(x) - mean) / sqrt(var + epsilon), -clip_obs,
+ * clip_obs)), IEEE float64 division and square root, no contraction: numpy's bits for the same statistics.  y may be
+ * x.  row_mask (optional device uint8 [rows]): only the rows with a non-zero byte are written (the terminal
+ * observations of the envs that reset, as ch_mlp_forward_masked).  With norm_obs off: y = x. */
+int ch_norm_obs_apply(const ch_norm* norm, const float* x, int64_t rows, const uint8_t* row_mask, float* y, void* stream);
+
+/* Replaces, for one env step: VecNormalize.step_wait's reward half -- when training, ret = ret * gamma + reward and
+ * ret_rms.update(ret) (with norm_reward off too); reward_out = float32(clip(float64(reward) / sqrt(ret_rms.var +
+ * epsilon), -clip_reward, clip_reward)) with the updated variance (norm_reward off: reward_out = reward); then
+ * ret = 0 where terminated | truncated.  reward / terminated / truncated: device [n_envs], n_envs = norm->n_envs.
+ * The raw reward is read only (reward_out must be another buffer): episode_stats and the episode ring keep reporting
+ * unnormalised returns, as SB3's Monitor sits under VecNormalize.  One launch of one workgroup up to 4096 envs; beyond
+ * that three (chunk moments, merge and update, elementwise). */
+int ch_norm_reward(const ch_norm* norm, const float* reward, const uint8_t* terminated, const uint8_t* truncated,
+                   int64_t n_envs, float* reward_out, void* stream);
+
+/* ch_rollout_collect_log under a normaliser (the native loop behind DeviceRolloutBuffer.collect(normalizer=...)):
+ * first obs_n = normalised step->obs under the statistics as they stand; then for t < n_steps the actor and critic
+ * forwards on obs_n, ch_rollout_store of obs_n (the buffer keeps normalised observations, as SB3's), ch_step with
+ * auto-reset and terminal observations, the optional ring record (raw returns), ch_norm_obs_update and
+ * ch_norm_obs_apply of the new observation into obs_n, the masked apply of the terminal observations (with the
+ * statistics already updated; they do not enter the update) and the masked critic on them, ch_norm_reward, and
+ * ch_rollout_post with the normalised reward; then the critic on obs_n and ch_rollout_gae.
+ * The forwards are the DENSE ch_mlp_forward, not ch_policy_forward: that one skips the input features past an env's
+ * NUM_DRONES because they are zero in the raw observation; normalised they are (0 - mean) / sqrt(var + epsilon), which
+ * is not zero wherever envs differ in NUM_DRONES.  A policy trained here must be evaluated the same way.
+ * The step fused with the next actor forward and the deferred bootstrap are not used.  norm == NULL is refused
+ * (CH_ERR_INVALID), as are a fused actor-critic (critic == NULL) and a MARL handle (CH_ERR_UNSUPPORTED), and
+ * norm->dim != obs_rows * 86 or norm->n_envs != n_envs (CH_ERR_INVALID).  obs_n, terminal_obs_n, reward_n required. */
+int ch_rollout_collect_norm(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* io, const ch_mlp* actor,
+                            const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
+                            int32_t bootstrap_truncated, const ch_ep_ring* ring, const ch_norm* norm, void* stream);
+
 /* ---- On-device rollout collection for the DTDE (RLlib) driver ----------------------------------------------
  * Replaces: RLlib PPO's sampling of RLlibMultiAgentWrapper envs with one shared policy over every agent
  * (DTDECattleHerder.py:62-97: policies = {"shared_policy"}, gamma 0.99, train_batch_size 4096; the wrapper's

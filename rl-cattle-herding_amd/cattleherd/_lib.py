@@ -32,7 +32,8 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark", "ch_eval_log_record", "ch_eval_log_run",
            "ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
            "ch_explained_variance_scratch", "ch_explained_variance", "ch_marl_ep_ring_begin", "ch_marl_ep_ring_record",
-           "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log", "ch_ppo_train_opt")
+           "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log", "ch_ppo_train_opt", "ch_norm_scratch_size",
+           "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward", "ch_rollout_collect_norm")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
@@ -49,6 +50,9 @@ CH_PPO_LOG_STATS = 6   # ch_ppo_train_log's columns: policy loss, value loss, me
 # target_kl / clip_range_vf (cattleherd/ppo.py): likewise
 _PPO_OPT_EXPORTS = ("ch_ppo_train_opt",)
 CH_PPO_OPT_STATS = 7   # ch_ppo_train_opt's columns: ch_ppo_train_log's six, then the step's state (1 applied, 0 tripped, -1 not run)
+# the device-side VecNormalize's (cattleherd/vec_normalize.py): likewise
+_NORM_EXPORTS = ("ch_norm_scratch_size", "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward",
+                 "ch_rollout_collect_norm")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -177,6 +181,14 @@ class ChMarlEpRing(ctypes.Structure):
     _fields_ = [("window", ctypes.c_int32), ("_pad", ctypes.c_int32)] + [(k, ctypes.c_void_p) for k in MARL_RING_ARRAYS]
 
 
+# the device-side VecNormalize (ch_norm_*; cattleherd/vec_normalize.py)
+class ChNorm(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("dim", "training", "norm_obs", "norm_reward")] + \
+        [(k, ctypes.c_double) for k in ("clip_obs", "clip_reward", "epsilon", "gamma")] + [("n_envs", ctypes.c_int64)] + \
+        [(k, ctypes.c_void_p) for k in ("mean", "var", "count", "ret_stats", "ret", "scratch")] + \
+        [("scratch_doubles", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in ("obs_n", "terminal_obs_n", "reward_n")]
+
+
 class ChError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcattleherd error {code}: {msg}")
@@ -275,7 +287,15 @@ def lib():
     if hasattr(L, "ch_ppo_train_opt"):
         L.ch_ppo_train_opt.argtypes = [P(ChPpoNet), P(ChPpoHparams), P(ChPpoData), P(ChPpoOpts), vp, i64, i64, vp, vp, vp,
                                        vp, vp, vp]
-    optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS + _PPO_OPT_EXPORTS
+    if hasattr(L, "ch_norm_begin"):
+        N = P(ChNorm)
+        L.ch_norm_scratch_size.argtypes = [i64, i32]
+        L.ch_norm_begin.argtypes = [N, vp]
+        L.ch_norm_obs_update.argtypes = [N, vp, i64, vp]
+        L.ch_norm_obs_apply.argtypes = [N, vp, i64, vp, vp, vp]
+        L.ch_norm_reward.argtypes = [N, vp, vp, vp, i64, vp, vp]
+    optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS + _PPO_OPT_EXPORTS + \
+        _NORM_EXPORTS
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in optional or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int
@@ -284,6 +304,8 @@ def lib():
     L.ch_marl_ppo_param_count.restype = L.ch_marl_ppo_scratch_size.restype = ctypes.c_int64
     if hasattr(L, "ch_explained_variance_scratch"):
         L.ch_explained_variance_scratch.restype = ctypes.c_int64
+    if hasattr(L, "ch_norm_scratch_size"):
+        L.ch_norm_scratch_size.restype = ctypes.c_int64
     _lib = L
     return L
 

@@ -111,9 +111,12 @@ class DeviceEvalTable:
                                              ctypes.byref(steps), ctypes.byref(rem), b._stream()), b.handle)
         return steps.value, rem.value
 
-    def run_steps(self, policy, max_steps, check_every=16, first_step_index=0):
+    def run_steps(self, policy, max_steps, check_every=16, first_step_index=0, normalizer=None):
         """The same loop driven from Python one kernel at a time (the loop the native call restates; kept for the
-        parity test): forward, clamp and slice, step, record; ``remaining`` read every ``check_every`` steps."""
+        parity test): forward, clamp and slice, step, record; ``remaining`` read every ``check_every`` steps.
+        ``normalizer`` (a ``vec_normalize.DeviceVecNormalize`` of this batch): the actor reads the observation
+        normalised with its statistics as they stand -- they are never updated here, as SB3 evaluates with
+        ``training=False`` -- through the dense forward (a normalised feature past ``NUM_DRONES`` is not zero)."""
         b = self.batch
         max_steps, check_every = int(max_steps), int(check_every)
         if max_steps < 1 or check_every < 1:
@@ -123,9 +126,14 @@ class DeviceEvalTable:
         w = b.num_drones * 4
         if actor.dims[-1] < w:
             raise ValueError(f"the actor's output ({actor.dims[-1]} wide) must be at least num_drones * 4 = {w} wide")
+        if normalizer is not None and getattr(normalizer, "batch", None) is not b:
+            raise ValueError("the normalizer belongs to another batch")
         t, rem = 0, -1
         while t < max_steps:
-            actor.forward_batch(b, mean)
+            if normalizer is None:
+                actor.forward_batch(b, mean)
+            else:
+                actor.forward(normalizer.normalize_obs(b.obs.view(b.n_envs, -1), out=normalizer.obs_n), mean)
             self.env_actions.copy_(mean[:, :w].clamp(-1.0, 1.0).reshape(b.n_envs, b.num_drones, 4))
             b.step(self.env_actions, autoreset=True, terminal_obs=False)
             self.record(first_step_index + t)
@@ -154,7 +162,7 @@ class DeviceEvalTable:
 
 
 def _evaluate(run, batch, policy, n_eval_episodes, max_steps, check_every, reset, return_episode_rewards,
-              monitor_rounding):
+              monitor_rounding, **run_kw):
     n = int(n_eval_episodes)
     per_env = -(-n // batch.n_envs)
     table = DeviceEvalTable(batch, max(per_env, 1))
@@ -163,7 +171,7 @@ def _evaluate(run, batch, policy, n_eval_episodes, max_steps, check_every, reset
     if reset:
         batch.reset()
     table.begin(n)
-    steps, remaining = getattr(table, run)(policy, max_steps, check_every)
+    steps, remaining = getattr(table, run)(policy, max_steps, check_every, **run_kw)
     if remaining != 0:
         raise RuntimeError(f"evaluate_policy: remaining = {remaining} of {n} episodes after max_steps = {steps} steps")
     returns, lengths = table.episodes()[:2]
@@ -190,11 +198,14 @@ def evaluate_policy(batch, policy, n_eval_episodes=5, max_steps=None, check_ever
 
 
 def evaluate_policy_steps(batch, policy, n_eval_episodes=5, max_steps=None, check_every=16, reset=True,
-                          return_episode_rewards=False, monitor_rounding=True):
+                          return_episode_rewards=False, monitor_rounding=True, normalizer=None):
     """``evaluate_policy`` driven from Python one kernel at a time (``DeviceEvalTable.run_steps``): the loop the native
-    call restates, kept for the parity tests, as ``collect_steps`` is for ``collect``."""
+    call restates, kept for the parity tests, as ``collect_steps`` is for ``collect``.  ``normalizer``: evaluate a
+    policy trained under a ``DeviceVecNormalize`` -- observations normalised with its frozen statistics, dense forward
+    (``run_steps``); the returns are the raw ones, as SB3 evaluates with ``norm_reward=False``."""
+    kw = {} if normalizer is None else {"normalizer": normalizer}
     return _evaluate("run_steps", batch, policy, n_eval_episodes, max_steps, check_every, reset, return_episode_rewards,
-                     monitor_rounding)
+                     monitor_rounding, **kw)
 
 
 class EvalLog:

@@ -43,6 +43,10 @@ def _bind():
     if hasattr(lib, "ch_rollout_collect_log"):   # (an older library, e.g. an A/B baseline loaded through CH_LIB_PATH, lacks it)
         lib.ch_rollout_collect_log.argtypes = lib.ch_rollout_collect.argtypes[:-1] + [ctypes.POINTER(L.ChEpRing), vp]
         lib.ch_rollout_collect_log.restype = ctypes.c_int
+    if hasattr(lib, "ch_rollout_collect_norm"):   # (likewise)
+        lib.ch_rollout_collect_norm.argtypes = lib.ch_rollout_collect.argtypes[:-1] + \
+            [ctypes.POINTER(L.ChEpRing), ctypes.POINTER(L.ChNorm), vp]
+        lib.ch_rollout_collect_norm.restype = ctypes.c_int
     return lib
 
 
@@ -73,15 +77,27 @@ class DeviceRolloutBuffer:
         self._rb = rb
         self._lib = _bind()
 
-    def collect(self, actor, critic, log_std, seed=0, bootstrap_truncated=True, ring=None):
+    def _check_normalizer(self, normalizer, critic):
+        if getattr(normalizer, "batch", None) is not self.batch:
+            raise ValueError("the normalizer belongs to another batch")
+        if critic is None:
+            raise ValueError("a fused actor-critic is not supported with a normalizer: pass the actor and the critic")
+
+    def collect(self, actor, critic, log_std, seed=0, bootstrap_truncated=True, ring=None, normalizer=None):
         """SB3 collect_rollouts for n_steps steps of every env, on the device, in one native call
         (ch_rollout_collect: the loop of collect_steps below runs in C++).  ``actor``: DevicePolicy of the
         action mean (no clip: SB3's action_net output), ``critic``: DevicePolicy of V, ``log_std``:
         float32 [act_dim] device tensor.  ``critic=None``: ``actor`` is a fused actor-critic
         (DevicePolicy.sb3_actor_critic / fuse, output [mean, value]) and one forward per step serves both.
         ``ring``: a ``train_log.EpisodeRing`` of this batch; every step's ended episodes are appended to it in env
-        order (ch_rollout_collect_log: one small launch more per step; the buffer's contents do not depend on it)."""
+        order (ch_rollout_collect_log: one small launch more per step; the buffer's contents do not depend on it).
+        ``normalizer``: a ``vec_normalize.DeviceVecNormalize`` of this batch (after its ``reset_obs()``): SB3's
+        ``VecNormalize`` around the env (ch_rollout_collect_norm) -- the buffer holds normalised observations and
+        rewards, the ring raw returns; the forwards are dense (``DevicePolicy.forward``, not ``forward_batch``), and a
+        fused actor-critic is refused (``ValueError``)."""
         b, lib = self.batch, self._lib
+        if normalizer is not None:
+            self._check_normalizer(normalizer, critic)
         torch = b.torch
         log_std = log_std.to(device=b.device, dtype=torch.float32).contiguous()
         for net in (actor, critic):
@@ -109,7 +125,10 @@ class DeviceRolloutBuffer:
                 None if critic is None else ctypes.byref(critic._net), log_std.data_ptr(), int(seed), self.gamma,
                 self.gae_lambda, int(bool(bootstrap_truncated)))
         try:
-            if ring is None:
+            if normalizer is not None:
+                L.check(lib.ch_rollout_collect_norm(*args, None if ring is None else ctypes.byref(ring._ring),
+                                                    ctypes.byref(normalizer._n), b._stream()), b.handle)
+            elif ring is None:
                 L.check(lib.ch_rollout_collect(*args, b._stream()), b.handle)
             else:
                 L.check(lib.ch_rollout_collect_log(*args, ctypes.byref(ring._ring), b._stream()), b.handle)
@@ -117,12 +136,19 @@ class DeviceRolloutBuffer:
             b._io.terminal_obs, b._io.reset_happened, b._io.episode_stats = keep
         return self
 
-    def collect_steps(self, actor, critic, log_std, seed=0, bootstrap_truncated=True, ring=None):
+    def collect_steps(self, actor, critic, log_std, seed=0, bootstrap_truncated=True, ring=None, normalizer=None,
+                      on_step=None):
         """The same collection driven from Python one kernel at a time (the reference loop the native
-        call restates; kept for the parity test).  ``ring``: as in ``collect`` (``ring.record()`` after each step)."""
+        call restates; kept for the parity test).  ``ring``: as in ``collect`` (``ring.record()`` after each step).
+        ``normalizer``: as in ``collect`` -- the loop ch_rollout_collect_norm restates, launch for launch;
+        ``on_step(t)`` is then called after step t's env step and before its normalisation (the parity test records
+        the raw step outputs there)."""
         b, lib, rb = self.batch, self._lib, ctypes.byref(self._rb)
         torch = b.torch
         log_std = log_std.to(device=b.device, dtype=torch.float32).contiguous()
+        if normalizer is not None:
+            self._check_normalizer(normalizer, critic)
+            return self._collect_steps_norm(actor, critic, log_std, seed, bootstrap_truncated, ring, normalizer, on_step)
         for t in range(self.T):
             actor.forward_batch(b, self.mean)
             critic.forward_batch(b, self.value)
@@ -140,6 +166,38 @@ class DeviceRolloutBuffer:
             L.check(lib.ch_rollout_post(b.handle, rb, t, b.reward.data_ptr(), b.terminated.data_ptr(),
                                         b.truncated.data_ptr(), tv, self.gamma, b._stream()), b.handle)
         critic.forward_batch(b, self.value)
+        L.check(lib.ch_rollout_gae(b.handle, rb, self.value.data_ptr(), self.gamma, self.gae_lambda, b._stream()),
+                b.handle)
+        return self
+
+
+    def _collect_steps_norm(self, actor, critic, log_std, seed, bootstrap_truncated, ring, n, on_step):
+        b, lib, rb = self.batch, self._lib, ctypes.byref(self._rb)
+        E = b.n_envs
+        raw, term = b.obs.view(E, -1), b.terminal_obs.view(E, -1)
+        n.normalize_obs(raw, out=n.obs_n)   # the env's observation under the statistics as they stand
+        for t in range(self.T):
+            actor.forward(n.obs_n, self.mean)       # dense: normalised features past NUM_DRONES are not zero
+            critic.forward(n.obs_n, self.value)
+            L.check(lib.ch_rollout_store(b.handle, rb, t, n.obs_n.data_ptr(), self.mean.data_ptr(), self.value.data_ptr(),
+                                         log_std.data_ptr(), int(seed), self.env_actions.data_ptr(), b._stream()),
+                    b.handle)
+            b.step(self.env_actions, autoreset=True, terminal_obs=True)
+            if ring is not None:
+                ring.record()
+            if on_step is not None:
+                on_step(t)
+            n.update_obs(raw)
+            n.normalize_obs(raw, out=n.obs_n)
+            tv = None
+            if bootstrap_truncated:
+                n.normalize_obs(term, out=n.terminal_obs_n, row_mask=b.reset_happened)
+                critic.forward(n.terminal_obs_n, self.terminal_value, row_mask=b.reset_happened)
+                tv = self.terminal_value.data_ptr()
+            n.step_reward(b.reward.view(E), b.terminated.view(E), b.truncated.view(E))
+            L.check(lib.ch_rollout_post(b.handle, rb, t, n.reward_n.data_ptr(), b.terminated.data_ptr(),
+                                        b.truncated.data_ptr(), tv, self.gamma, b._stream()), b.handle)
+        critic.forward(n.obs_n, self.value)
         L.check(lib.ch_rollout_gae(b.handle, rb, self.value.data_ptr(), self.gamma, self.gae_lambda, b._stream()),
                 b.handle)
         return self

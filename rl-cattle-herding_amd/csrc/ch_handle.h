@@ -1,7 +1,8 @@
 // ch_handle.h — the handle behind the C ABI, private to its host files: ch_api.cpp (config, create / destroy, reset,
 // step, state, metrics, host output), ch_api_policy.cpp (policy forwards, PPO and MARL rollout collection),
 // ch_api_eval.cpp (the on-device evaluate_policy and the DTDE driver's evaluation), ch_api_eval_log.cpp (the device-side
-// evaluator log) and ch_api_train_log.cpp (the SB3 and the RLlib training log).
+// evaluator log), ch_api_train_log.cpp (the SB3 and the RLlib training log) and ch_api_norm.cpp (the device-side
+// VecNormalize and the collection under it).
 #pragma once
 #include <string>
 #include <vector>
