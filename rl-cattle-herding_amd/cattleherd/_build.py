@@ -13,13 +13,13 @@ BUILD = os.path.join(ROOT, "build")
 LIB = os.path.join(PKG, "libcattleherd.so")
 SOURCES = ["ch_kernels.hip", "ch_step.hip", "ch_step_multi.hip", "ch_policy.hip", "ch_aux.hip", "ch_ppo.hip", "ch_eval.hip",
            "ch_marl_eval.hip", "ch_eval_log.hip", "ch_ep_ring.hip", "ch_marl_ep_ring.hip", "ch_norm.hip", "ch_api.cpp", "ch_api_policy.cpp", "ch_api_ppo.cpp", "ch_api_eval.cpp",
-           "ch_api_eval_log.cpp", "ch_api_train_log.cpp", "ch_api_norm.cpp", "ch_mlp_plan.cpp"]
+           "ch_api_eval_log.cpp", "ch_api_train_log.cpp", "ch_api_norm.cpp", "ch_mlp_plan.cpp", "ch_step_plan.cpp"]
 # per-source flags: ch_step_multi.hip's step loop keeps k_step2's register allocation only with machine LICM off
 # (ch_step_multi.hip header)
 SOURCE_FLAGS = {"ch_step_multi.hip": ["-mllvm", "-disable-machine-licm"]}
 HEADERS = ["ch_device.h", "ch_internal.h", "ch_common.h", "ch_spawn_table.inc", "ch_mlp2_dev.h", "ch_rollout_dev.h",
            "ch_episode_dev.h", "ch_step_body.h", "ch_step_sync.h", "ch_step_flock.h", "ch_handle.h", "ch_ppo.h",
-           "ch_ppo_fb_body.inc", "ch_ppo_dw_body.inc", "ch_ppo_adam_body.inc", "ch_mlp_plan.h", "ch_norm.h"]
+           "ch_ppo_fb_body.inc", "ch_ppo_dw_body.inc", "ch_ppo_adam_body.inc", "ch_mlp_plan.h", "ch_norm.h", "ch_step_plan.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("CH_OFFLOAD_ARCH", "gfx950")
 # fp-contract off: the fp64 path keeps the reference's rounding (no fused multiply-adds), so it

@@ -252,6 +252,13 @@ def lib():
         L.ch__ppo_kernel.restype = ctypes.c_char_p
         L.ch__ppo_last_step.argtypes = [P(i32 * 5)]
         L.ch__ppo_plan.restype = L.ch__ppo_last_step.restype = ctypes.c_int
+    if hasattr(L, "ch__step_plan"):   # internal: the env step's host-only planner and kernel table, see step_plan below
+        L.ch__step_plan.argtypes = [i32, i32, i32, i32, i32, i64, i32, i64, i32, i32, i32, P(i64 * 13)]
+        L.ch__step_plan_of.argtypes = [vp, P(i64 * 13)]
+        L.ch__step_kernel.argtypes = [i32, P(i32 * 11)]
+        L.ch__step_rule.argtypes = [i32]
+        L.ch__step_kernel.restype = L.ch__step_rule.restype = ctypes.c_char_p
+        L.ch__step_plan.restype = L.ch__step_plan_of.restype = ctypes.c_int
     for pre, (N, H, D) in (("ch_ppo_", (P(ChPpoNet), P(ChPpoHparams), P(ChPpoData))),
                            ("ch_marl_ppo_", (P(ChMarlPpoNet), P(ChMarlPpoHparams), P(ChMarlPpoData)))):
         getattr(L, pre + "param_count").argtypes = [N]
@@ -400,6 +407,70 @@ def ppo_last_step():
     check(lib().ch__ppo_last_step(ctypes.byref(out)))
     names = ppo_kernel_table()
     return names[out[0]], names[out[1]], names[out[2]], int(out[3]), int(out[4])
+
+
+# Internal (tests / diagnostics): the step kernels' table (csrc/ch_step_plan.h kStepTable), one name per instantiation
+# of k_step2<R, MODE, GT, NT, MT, PHYS, PW, TOBS>, k_step2_multi<R, MODE, GT, NT, MT, PHYS, PW, WPE> and
+# k_step2_actor<R, MODE, GT, NT, MT, TOBS> (trailing default arguments left out); a plan's rows index it
+_STEP2 = ("1,0,0,0,true", "0,16,4,16,true", "0,0,0,0,true", "1,16,4,32,false,true", "1,0,0,0,false,true",
+          "0,0,0,0,false,true", "1,0,0,0", "0,8,4,16", "0,16,4,16,false,false,true", "0,16,4,16", "0,16,2,8", "0,4,2,8",
+          "0,0,0,0")
+STEP_KERNELS = tuple(f"k_step2<{r},{a}>" for r in ("double", "float") for a in _STEP2) + (
+    "k_step2_multi<double,1,16,4,32,false,true>", "k_step2_multi<double,0,16,4,16>", "k_step2_multi<double,0,8,4,16>",
+    "k_step2_multi<double,0,16,2,8>", "k_step2_multi<double,0,4,2,8>", "k_step2_multi<float,0,16,4,16,false,false,4>",
+    "k_step2_multi<float,0,16,4,16>", "k_step2_actor<double,0,16,4,16,false>", "k_step2_actor<double,0,16,4,16,true>")
+STEP_KERNEL_COLUMNS = ("family", "precision", "mode", "gt", "nt", "mt", "phys", "pw", "tobs_wpe", "max_block", "pipelined")
+# the planner's geometry rules in the order it applies them (ch__step_rule); bit r of a plan's "rules": rule r fired
+STEP_RULES = ("generic", "4x16", "2x8", "per_wave", "sep", "v1_fallback")
+STEP_PLAN_COLUMNS = ("kernel", "G", "block", "lds", "pw", "sep", "step_row", "step_row_tobs", "multi_row", "multi_block",
+                     "multi_lds", "fused_actor", "rules")
+
+
+def step_kernel_table():
+    """Internal (tests / diagnostics): the library's step-kernel table, one dict per row: its name and
+    STEP_KERNEL_COLUMNS (family: 0 k_step2, 1 k_step2_multi, 2 k_step2_actor; tobs_wpe: TOBS, for k_step2_multi WPE)."""
+    rows = []
+    while True:
+        out = (ctypes.c_int32 * 11)()
+        name = lib().ch__step_kernel(len(rows), ctypes.byref(out))
+        if name is None:
+            return rows
+        rows.append(dict(zip(STEP_KERNEL_COLUMNS, (int(v) for v in out)), name=name.decode()))
+
+
+def step_rules():
+    """Internal (tests / diagnostics): the names of the planner's geometry rules, in order (ch__step_rule)."""
+    names = []
+    while (name := lib().ch__step_rule(len(names))) is not None:
+        names.append(name.decode())
+    return tuple(names)
+
+
+def _step_plan_dict(out):
+    d = dict(zip(STEP_PLAN_COLUMNS, (int(v) for v in out)))
+    d["rules"] = tuple(n for r, n in enumerate(STEP_RULES) if d["rules"] >> r & 1)
+    return d
+
+
+def step_plan(mode, num_drones, num_cattle, precision, physics, n_envs, cus, lds_budget, kernel=0, geometry=(0, 0)):
+    """Internal (tests / diagnostics): what ch_create plans for a handle of this shape on a device of ``cus`` compute
+    units with ``lds_budget`` bytes of LDS per workgroup (csrc/ch_step_plan.cpp step_plan; host only, no device needed);
+    ``kernel`` / ``geometry``: as after ch__set_kernel / ch__set_geometry.  Returns a dict of STEP_PLAN_COLUMNS (rows
+    index STEP_KERNELS, -1: none; rules: the names of the geometry rules that fired).  Raises ``ChError`` with the code
+    the setter would return when the planner refuses the overrides."""
+    out = (ctypes.c_int64 * 13)()
+    rc = lib().ch__step_plan(mode, num_drones, num_cattle, precision, physics, n_envs, cus, lds_budget, kernel,
+                             geometry[0], geometry[1], ctypes.byref(out))
+    if rc != CH_OK:
+        raise ChError(rc, "ch__step_plan")
+    return _step_plan_dict(out)
+
+
+def step_plan_of(handle):
+    """Internal (tests): the plan a handle holds (ch__step_plan_of), as step_plan returns it."""
+    out = (ctypes.c_int64 * 13)()
+    check(lib().ch__step_plan_of(handle, ctypes.byref(out)), handle)
+    return _step_plan_dict(out)
 
 
 def default_config(mode, num_drones, num_cattle):

@@ -25,8 +25,6 @@ thread_local std::string g_create_err;
 
 // episode_length per curriculum level (curriculum_learning.py:24-182)
 static const double kEpisodeLen[8] = {40, 40, 40, 40, 80, 40, 80, 80};
-static const int kLevelMin[8] = {3, 4, 4, 4, 4, 4, 4, 4};
-static const int kLevelMax[8] = {3, 4, 4, 4, 4, 4, 12, 12};
 
 // --------------------------------------------------------------------------------------------
 // Spawn table.  Cows 0..15 of every scenario come from config/cattle_positions.yaml (the
@@ -111,8 +109,8 @@ static StepParams<R> params(ch_handle* h) {
     p.pos64 = h->pos64; p.cpos64 = h->cpos64; p.prev64 = h->prev64;
     p.metrics = h->metrics; p.spawn = h->spawn; p.n_scen = h->n_scen; p.n_cows = h->n_cows;
     p.debug = h->debug;
-    p.phase_mask = h->phase_mask;
-    p.G = h->G; p.P = h->P; p.pairs = h->pairs; p.pw = h->pw; p.sep = h->sep;
+    p.phase_mask = h->ov.phase_mask;
+    p.G = h->plan.G; p.P = h->P; p.pairs = h->pairs; p.pw = h->plan.pw; p.sep = h->plan.sep;
     p.tstamp = h->tstamp;
     p.physics = c.physics; p.gnd_h_clip = gnd_eff_h_clip(); p.phys = (R*)h->phys;
     p.err = h->errw;
@@ -120,11 +118,30 @@ static StepParams<R> params(ch_handle* h) {
     return p;
 }
 
-// the v2 step's once-per-device function attribute, set outside any stream capture
-static hipError_t prepare_step(ch_handle* h) {
-    if (h->kernel != 2) return hipSuccess;
-    if (h->rsize == sizeof(double)) return launch_step_v2(params<double>(h), h->block, h->lds, nullptr, false);
-    return launch_step_v2(params<float>(h), h->block, h->lds, nullptr, false);
+// f(params<R>(h)) for the handle's precision
+template <class F>
+static auto with_params(ch_handle* h, F&& f) {
+    return h->rsize == sizeof(double) ? f(params<double>(h)) : f(params<float>(h));
+}
+
+// Plans the handle's step under the overrides `ov` (ch_step_plan.h) and, when the planner takes them, stores both and
+// sets the v2 step rows' once-per-device function attribute, outside any stream capture.  CH_ERR_INVALID /
+// CH_ERR_UNSUPPORTED: the planner refused the overrides and the handle is as it was.
+static int replan(ch_handle* h, const StepOverrides& ov) {
+    const ch_config& c = h->cfg;
+    const StepPlan pl = step_plan({c.mode, h->NC, h->M, c.precision, c.physics, h->E}, h->cus, h->lds_budget, ov);
+    if (pl.error) return pl.error;
+    h->plan = pl;
+    h->ov = ov;
+    hipError_t e = hipSuccess;
+    if (pl.kernel == 2)
+        e = with_params(h, [&](auto p) {
+            hipError_t e2 = launch_step_v2(p, pl.step_row[0], pl.block, pl.lds, nullptr, false);
+            if (e2 == hipSuccess && pl.step_row[1] != pl.step_row[0])
+                e2 = launch_step_v2(p, pl.step_row[1], pl.block, pl.lds, nullptr, false);
+            return e2;
+        });
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_DEVICE, std::string("prepare_step(h): ") + hipGetErrorString(e));
 }
 
 extern "C" {
@@ -210,11 +227,11 @@ int device_status(ch_handle* h, int word) {
                                                   : ""));
 }
 
-extern "C" {
+// ch_create in three parts: the configuration's checks (the reference constructors'), the device arrays with the state
+// the constructors leave behind, and the step's plan.
 
-int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** out) {
-    if (!c || !out) return fail(nullptr, CH_ERR_INVALID, "ch_create: NULL argument");
-    *out = nullptr;
+// `level`, `mn`, `mx`: the curriculum level and the drone-count bounds with their defaults filled in
+static int validate_config(const ch_config* c, int64_t n_envs, int& level, int& mn, int& mx) {
     if (c->abi_version != CH_ABI_VERSION) return fail(nullptr, CH_ERR_INVALID, "ch_create: abi_version mismatch");
     if (c->mode != CH_MODE_CTDE && c->mode != CH_MODE_MARL) return fail(nullptr, CH_ERR_INVALID, "ch_create: bad mode");
     if (c->physics < CH_PHYS_PYB || c->physics > CH_PHYS_DYN_RK4)
@@ -228,10 +245,10 @@ int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** ou
         return fail(nullptr, CH_ERR_INVALID, "[ERROR] in BaseAviary.__init__(), pyb_freq is not divisible by env_freq.");
     if (c->precision != CH_PREC_F64 && c->precision != CH_PREC_F32)
         return fail(nullptr, CH_ERR_INVALID, "ch_create: bad precision");
-    int level = c->curriculum_level < 0 ? (c->mode == CH_MODE_CTDE ? 7 : 0) : c->curriculum_level;
+    level = c->curriculum_level < 0 ? (c->mode == CH_MODE_CTDE ? 7 : 0) : c->curriculum_level;
     if (level > 7) return fail(nullptr, CH_ERR_INVALID, "ch_create: curriculum_level must be in [0, 7]");
-    int mn = c->min_drones < 0 ? c->num_drones : c->min_drones;
-    int mx = c->max_drones < 0 ? c->num_drones : c->max_drones;
+    mn = c->min_drones < 0 ? c->num_drones : c->min_drones;
+    mx = c->max_drones < 0 ? c->num_drones : c->max_drones;
     if (mn < 1 || mx < mn || mx > c->num_drones)
         return fail(nullptr, CH_ERR_INVALID,
                     "ch_create: need 1 <= min_drones <= max_drones <= num_drones (the reference indexes "
@@ -242,6 +259,120 @@ int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** ou
                     "CattleAviary.py:234); use compat=0");
     if (c->spawn_table && (c->spawn_scenarios < 1 || c->spawn_cows < c->num_cattle))
         return fail(nullptr, CH_ERR_INVALID, "ch_create: spawn table smaller than num_cattle");
+    return CH_OK;
+}
+
+#define CTRY(expr)                                                                                  \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) {                                                                     \
+            h->err = std::string(#expr) + ": " + hipGetErrorString(_e);                             \
+            return _e;                                                                              \
+        }                                                                                           \
+    } while (0)
+
+// the handle's device arrays, the spawn table and the cow-pair list; the failed call and its error in h->err
+static hipError_t allocate_state(ch_handle* h) {
+    const ch_config* c = &h->cfg;
+    const int64_t E = h->E;
+    CTRY(hipMalloc(&h->drone, h->rsize * kDroneComps * E * h->NC));
+    CTRY(hipMalloc(&h->rpy, h->rsize * 3 * E * h->NC));
+    CTRY(hipMalloc(&h->cattle, h->rsize * kCattleComps * E * h->M));
+    CTRY(hipMalloc(&h->phys, h->rsize * kPhysComps * E * h->NC));
+    CTRY(hipMemset(h->phys, 0, h->rsize * kPhysComps * E * h->NC));
+    CTRY(hipMalloc(&h->envr, h->rsize * kEnvReal * E));
+    if (h->rsize == sizeof(float)) {
+        CTRY(hipMalloc(&h->pos64, sizeof(double) * 3 * E * h->NC));
+        CTRY(hipMalloc(&h->cpos64, sizeof(double) * 2 * E * h->M));
+        CTRY(hipMalloc(&h->prev64, sizeof(double) * E));
+    }
+    CTRY(hipMalloc(&h->envi, sizeof(int) * kEnvInt * E));
+    CTRY(hipMalloc(&h->metrics, sizeof(double) * kMetricRows * E));
+    CTRY(hipMalloc(&h->stale, 2 * (size_t)E));
+    CTRY(hipMemset(h->stale, 1, 2 * (size_t)E));   // no Euler cache yet; obs bytes unknown
+    CTRY(hipMalloc(&h->obs_tag, sizeof(unsigned long long) * (size_t)E));
+    CTRY(hipMemset(h->obs_tag, 0, sizeof(unsigned long long) * (size_t)E));   // no buffer holds them
+    if (c->eval_metrics) {
+        CTRY(hipMalloc(&h->evald, sizeof(double) * E * h->NC));
+        CTRY(hipMemset(h->evald, 0, sizeof(double) * E * h->NC));
+    }
+    CTRY(hipMalloc(&h->errw, sizeof(int)));
+    CTRY(hipMemset(h->errw, 0, sizeof(int)));
+    CTRY(hipMalloc(&h->mdev, sizeof(double) * (CH_METRIC_COUNT + 1)));
+    CTRY(hipHostMalloc(&h->mhost, sizeof(double) * (CH_METRIC_COUNT + 1), hipHostMallocDefault));
+
+    std::vector<double> table;
+    if (c->spawn_table) {
+        table.assign(c->spawn_table, c->spawn_table + (size_t)c->spawn_scenarios * c->spawn_cows * 2);
+        h->n_scen = c->spawn_scenarios;
+        h->n_cows = c->spawn_cows;
+    } else {
+        table = make_spawn_table(h->M);
+        h->n_scen = CH_SPAWN_SCENARIOS;
+        h->n_cows = std::max(h->M, (int)CH_SPAWN_COWS);
+    }
+    CTRY(hipMalloc(&h->spawn, table.size() * sizeof(double)));
+    CTRY(hipMemcpy(h->spawn, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<uint16_t> pl((size_t)std::max(h->P, 1));
+    for (int i = 0, r = 0; i < h->M; ++i)
+        for (int j = i + 1; j < h->M; ++j) pl[r++] = (uint16_t)(i | (j << 8));
+    CTRY(hipMalloc(&h->pairs, pl.size() * sizeof(uint16_t)));
+    CTRY(hipMemcpy(h->pairs, pl.data(), pl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return hipSuccess;
+}
+
+// initial state = what the constructors leave behind before the first reset():
+// identity quaternions, zero PID state, spawn index advanced once by __init__'s _housekeeping.
+static hipError_t initial_state(ch_handle* h) {
+    const int64_t E = h->E;
+    std::vector<double> dz((size_t)kDroneComps * E * h->NC, 0.0);
+    for (int64_t i = 0; i < E * h->NC; ++i) {
+        dz[(size_t)6 * E * h->NC + i] = 1.0;
+        dz[(size_t)25 * E * h->NC + i] = 1.0;   // cached link frame: identity too
+    }
+    std::vector<int> ei((size_t)kEnvInt * E, 0);
+    for (int64_t e = 0; e < E; ++e) {
+        ei[4 * E + e] = h->start_level;
+        ei[6 * E + e] = (int)((1 + h->cfg.env_id_offset + e) % h->n_scen);
+    }
+    std::vector<double> cz((size_t)kCattleComps * E * h->M, 0.0), rz((size_t)kEnvReal * E, 0.0);
+    if (h->rsize == sizeof(double)) {
+        CTRY(hipMemcpy(h->drone, dz.data(), dz.size() * 8, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->cattle, cz.data(), cz.size() * 8, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->envr, rz.data(), rz.size() * 8, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> f(dz.begin(), dz.end()), fc(cz.begin(), cz.end()), fr(rz.begin(), rz.end());
+        CTRY(hipMemcpy(h->drone, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->cattle, fc.data(), fc.size() * 4, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->envr, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->pos64, dz.data(), sizeof(double) * 3 * E * h->NC, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->cpos64, cz.data(), sizeof(double) * 2 * E * h->M, hipMemcpyHostToDevice));
+        CTRY(hipMemcpy(h->prev64, rz.data(), sizeof(double) * E, hipMemcpyHostToDevice));
+    }
+    CTRY(hipMemcpy(h->envi, ei.data(), ei.size() * sizeof(int), hipMemcpyHostToDevice));
+    CTRY(hipMemset(h->metrics, 0, sizeof(double) * kMetricRows * E));
+    return hipSuccess;
+}
+
+// what the planner plans for: the device's CU count and its LDS per CU, capped at what the step kernels opt in to
+static hipError_t device_limits(ch_handle* h) {
+    int cus = 256, lds_max = 64 * 1024;
+    CTRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device) != hipSuccess)
+        lds_max = 64 * 1024;
+    h->cus = cus;
+    h->lds_budget = std::min<size_t>((size_t)lds_max, kStepLdsMax);
+    return hipSuccess;
+}
+#undef CTRY
+
+extern "C" {
+
+int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** out) {
+    if (!c || !out) return fail(nullptr, CH_ERR_INVALID, "ch_create: NULL argument");
+    *out = nullptr;
+    int level = 0, mn = 0, mx = 0;
+    if (int rc = validate_config(c, n_envs, level, mn, mx)) return rc;
     int dev_count = 0;
     hipError_t ge = hipGetDeviceCount(&dev_count);
     if (ge != hipSuccess || dev_count == 0)
@@ -266,7 +397,6 @@ int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** ou
     h->episode_len = kEpisodeLen[level];
     h->rsize = c->precision == CH_PREC_F64 ? sizeof(double) : sizeof(float);
     h->P = h->M * (h->M - 1) / 2;
-    (void)kLevelMin; (void)kLevelMax;
     {   // ch_rollout_collect's path: the environment's choice, ch__set_rollout_path overrides it per handle
         const char* v = getenv("CH_ROLLOUT_COPY");
         const char* k = getenv("CH_ROLLOUT_STORE_KERNEL");
@@ -274,163 +404,19 @@ int ch_create(const ch_config* c, int64_t n_envs, int32_t device, ch_handle** ou
         h->ro.path = ((v && v[0] == '1') ? 1 : 0) | ((k && k[0] == '1') ? 2 : 0) | ((f && f[0] == '1') ? 4 : 0);
     }
 
-    auto cleanup = [&](int code) { free_all(h); std::string m = h->err; delete h; g_create_err = m; return code; };
-#define CTRY(expr)                                                                                  \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            h->err = std::string(#expr) + ": " + hipGetErrorString(_e);                             \
-            return cleanup(_e == hipErrorOutOfMemory ? CH_ERR_NOMEM : CH_ERR_DEVICE);               \
-        }                                                                                           \
-    } while (0)
-    CTRY(hipSetDevice(device));
-    const int64_t E = h->E;
-    CTRY(hipMalloc(&h->drone, h->rsize * kDroneComps * E * h->NC));
-    CTRY(hipMalloc(&h->rpy, h->rsize * 3 * E * h->NC));
-    CTRY(hipMalloc(&h->cattle, h->rsize * kCattleComps * E * h->M));
-    CTRY(hipMalloc(&h->phys, h->rsize * kPhysComps * E * h->NC));
-    CTRY(hipMemset(h->phys, 0, h->rsize * kPhysComps * E * h->NC));
-    CTRY(hipMalloc(&h->envr, h->rsize * kEnvReal * E));
-    if (h->rsize == sizeof(float)) {
-        CTRY(hipMalloc(&h->pos64, sizeof(double) * 3 * E * h->NC));
-        CTRY(hipMalloc(&h->cpos64, sizeof(double) * 2 * E * h->M));
-        CTRY(hipMalloc(&h->prev64, sizeof(double) * E));
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) h->err = std::string("hipSetDevice(device): ") + hipGetErrorString(e);
+    if (e == hipSuccess) e = allocate_state(h);
+    if (e == hipSuccess) e = initial_state(h);
+    if (e == hipSuccess) e = device_limits(h);
+    int rc = e == hipSuccess ? CH_OK : e == hipErrorOutOfMemory ? CH_ERR_NOMEM : CH_ERR_DEVICE;
+    if (rc == CH_OK) rc = replan(h, StepOverrides{});   // (the rules alone always plan)
+    if (rc != CH_OK) {
+        free_all(h);
+        g_create_err = h->err;
+        delete h;
+        return rc;
     }
-    CTRY(hipMalloc(&h->envi, sizeof(int) * kEnvInt * E));
-    CTRY(hipMalloc(&h->metrics, sizeof(double) * kMetricRows * E));
-    {
-        CTRY(hipMalloc(&h->stale, 2 * (size_t)E));
-        CTRY(hipMemset(h->stale, 1, 2 * (size_t)E));   // no Euler cache yet; obs bytes unknown
-        CTRY(hipMalloc(&h->obs_tag, sizeof(unsigned long long) * (size_t)E));
-        CTRY(hipMemset(h->obs_tag, 0, sizeof(unsigned long long) * (size_t)E));   // no buffer holds them
-    }
-    if (c->eval_metrics) {
-        CTRY(hipMalloc(&h->evald, sizeof(double) * E * h->NC));
-        CTRY(hipMemset(h->evald, 0, sizeof(double) * E * h->NC));
-    }
-    CTRY(hipMalloc(&h->errw, sizeof(int)));
-    CTRY(hipMemset(h->errw, 0, sizeof(int)));
-    CTRY(hipMalloc(&h->mdev, sizeof(double) * (CH_METRIC_COUNT + 1)));
-    CTRY(hipHostMalloc(&h->mhost, sizeof(double) * (CH_METRIC_COUNT + 1), hipHostMallocDefault));
-
-    std::vector<double> table;
-    if (c->spawn_table) {
-        table.assign(c->spawn_table, c->spawn_table + (size_t)c->spawn_scenarios * c->spawn_cows * 2);
-        h->n_scen = c->spawn_scenarios;
-        h->n_cows = c->spawn_cows;
-    } else {
-        table = make_spawn_table(h->M);
-        h->n_scen = CH_SPAWN_SCENARIOS;
-        h->n_cows = std::max(h->M, (int)CH_SPAWN_COWS);
-    }
-    CTRY(hipMalloc(&h->spawn, table.size() * sizeof(double)));
-    {
-        // v2 geometry: G envs per workgroup with all G*N drone chains in wave 0, the LDS
-        // carve within the per-CU budget, and at least one workgroup per CU when E allows it.
-        int cus = 256, lds_max = 64 * 1024;
-        CTRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess)
-            lds_max = 64 * 1024;
-        const size_t budget = std::min<size_t>((size_t)lds_max, 160 * 1024);
-        // a drone wave (G*N <= 64 drone chains) plus three cow waves (G*M cows, one per lane when it fits)
-        int G = std::max(1, std::min(64 / h->NC, 192 / h->M));
-        G = (int)std::min<int64_t>(G, std::max<int64_t>(1, E / std::max(cus, 1)));
-        while (G & (G - 1)) G &= G - 1;   // power of two: whole workgroups per CU at E = 2^k
-        while (G > 1 && V2Layout(G, h->NC, h->M, h->P, c->mode, (int)h->rsize).bytes() > budget) --G;
-        h->G = G;
-        h->lds = V2Layout(G, h->NC, h->M, h->P, c->mode, (int)h->rsize).bytes();
-        h->block = 256;
-        // measured (tools/geom_sweep.py, profiles/r02/geom_*.log): at 4 drones x 16 cattle one workgroup
-        // of 16 envs per CU (a full 64-drone wave + cow waves sharing the work counters) beats two of 8
-        // envs, and 11 cow waves (768 threads, 3 waves per SIMD) edge out 7 (24.1 vs 24.8 us at 4096 envs);
-        // the physics variants keep 512 (their register use allows 2 waves per SIMD)
-        if (c->mode == CH_MODE_CTDE && h->NC == 4 && h->M == 16 && E >= 16 * (int64_t)cus &&
-            V2Layout(16, 4, 16, h->P, c->mode, (int)h->rsize).bytes() <= budget) {
-            h->G = 16;
-            h->lds = V2Layout(16, 4, 16, h->P, c->mode, (int)h->rsize).bytes();
-            // f32: 512 threads (tools/f32_geom_probe.py: 419 vs 273 M env-steps/s at 262144 envs, 1.5 % slower
-            // at 4096; f64 keeps 768, 230 vs 225 M at 262144 and 1 % faster at 4096)
-            h->block = (c->physics == CH_PHYS_PYB && h->rsize == 8) ? CH_V2_MAX_BLOCK : CH_V2_MAX_BLOCK_PW;
-        }
-        // 2 drones x 8 cattle (configs[1]/[2]), f64: 16 envs / 512 threads per workgroup from 1024 envs up, also when
-        // that leaves CUs idle (configs[1]: 64 workgroups) -- tools/multi_geom.py, profiles/r06/ab/r6y_*: at 1024 envs
-        // 78.1 vs 76.4 M env-steps/s (ch_step_n) and 61.8 vs 58.5 M (ch_step) against 4 envs / 256 threads; at 4096
-        // envs 311.9 vs 311.0 M and 238.3 vs 229.4 M against 16 envs / 256 threads
-        if (c->mode == CH_MODE_CTDE && h->NC == 2 && h->M == 8 && h->rsize == 8 && c->physics == CH_PHYS_PYB &&
-            E >= 1024 && V2Layout(16, 2, 8, h->P, c->mode, (int)h->rsize).bytes() <= budget) {
-            h->G = 16;
-            h->lds = V2Layout(16, 2, 8, h->P, c->mode, (int)h->rsize).bytes();
-            h->block = CH_V2_MAX_BLOCK_PW;
-        }
-        // measured (tools/ab/marl.py, MI355X, 4096 envs): the dataflow kernel wins for every CTDE size
-        // (2x8 19.4 vs 41.1 us, 8x16 39.7 vs 55.8, 12x16 59.9 vs 67.1) and for MARL with up to 16
-        // cattle (3x8 25.8 vs 43.2).  Above 16 cows one shared pair table per workgroup (15.9 KB per
-        // env at 32 cows) leaves room for 4 envs per CU; the per-wave env tables (V2Layout W) keep a
-        // CU's 16 envs in one workgroup instead.
-        if (h->M >= kPwMinCattle) {
-            h->kernel = 1;   // unless a per-wave geometry fits (physics variants stay on v1)
-            if (c->physics == CH_PHYS_PYB) {
-                const int cand[][2] = {{16, 512}, {8, 512}, {8, 256}, {4, 256}, {2, 128}, {1, 128}};
-                for (const auto& gb : cand) {
-                    const int g = gb[0], blk = gb[1];
-                    if (g * h->NC > 64 || g * h->M > 3 * (blk - 64)) continue;
-                    if (g > 1 && E < (int64_t)g * cus) continue;
-                    const size_t l = V2Layout(g, h->NC, h->M, h->P, c->mode, (int)h->rsize, blk / 64 - 1).bytes();
-                    if (l > budget) continue;
-                    h->G = g; h->block = blk; h->lds = l; h->pw = true; h->kernel = 2;
-                    break;
-                }
-            }
-        }
-        // shared tables: the shepherd terms in their own region when it fits, so they need not wait for every
-        // alpha row to have read the pair table
-        if (!h->pw) {
-            const size_t l = V2Layout(h->G, h->NC, h->M, h->P, c->mode, (int)h->rsize, 0, true).bytes();
-            if (l <= budget) { h->sep = true; h->lds = l; }
-        }
-        if (h->lds > budget) h->kernel = 1;   // one env's pair table alone exceeds the budget
-        std::vector<uint16_t> pl((size_t)std::max(h->P, 1));
-        for (int i = 0, r = 0; i < h->M; ++i)
-            for (int j = i + 1; j < h->M; ++j) pl[r++] = (uint16_t)(i | (j << 8));
-        CTRY(hipMalloc(&h->pairs, pl.size() * sizeof(uint16_t)));
-        CTRY(hipMemcpy(h->pairs, pl.data(), pl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    CTRY(hipMemcpy(h->spawn, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
-
-    // initial state = what the constructors leave behind before the first reset():
-    // identity quaternions, zero PID state, spawn index advanced once by __init__'s _housekeeping.
-    std::vector<double> dz((size_t)kDroneComps * E * h->NC, 0.0);
-    for (int64_t i = 0; i < E * h->NC; ++i) {
-        dz[(size_t)6 * E * h->NC + i] = 1.0;
-        dz[(size_t)25 * E * h->NC + i] = 1.0;   // cached link frame: identity too
-    }
-    std::vector<int> ei((size_t)kEnvInt * E, 0);
-    for (int64_t e = 0; e < E; ++e) {
-        ei[4 * E + e] = level;
-        ei[6 * E + e] = (int)((1 + c->env_id_offset + e) % h->n_scen);
-    }
-    int rc = 0;
-    {
-        std::vector<double> cz((size_t)kCattleComps * E * h->M, 0.0), rz((size_t)kEnvReal * E, 0.0);
-        if (h->rsize == sizeof(double)) {
-            CTRY(hipMemcpy(h->drone, dz.data(), dz.size() * 8, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->cattle, cz.data(), cz.size() * 8, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->envr, rz.data(), rz.size() * 8, hipMemcpyHostToDevice));
-        } else {
-            std::vector<float> f(dz.begin(), dz.end()), fc(cz.begin(), cz.end()), fr(rz.begin(), rz.end());
-            CTRY(hipMemcpy(h->drone, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->cattle, fc.data(), fc.size() * 4, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->envr, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->pos64, dz.data(), sizeof(double) * 3 * E * h->NC, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->cpos64, cz.data(), sizeof(double) * 2 * E * h->M, hipMemcpyHostToDevice));
-            CTRY(hipMemcpy(h->prev64, rz.data(), sizeof(double) * E, hipMemcpyHostToDevice));
-        }
-        CTRY(hipMemcpy(h->envi, ei.data(), ei.size() * sizeof(int), hipMemcpyHostToDevice));
-        CTRY(hipMemset(h->metrics, 0, sizeof(double) * kMetricRows * E));
-    }
-    (void)rc;
-    CTRY(prepare_step(h));
-#undef CTRY
     *out = h;
     return CH_OK;
 }
@@ -470,36 +456,18 @@ static int clear_error_word(ch_handle* h, hipStream_t st, const char* who) {
     return CH_OK;
 }
 
-int ch_reset(ch_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
-    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_reset: NULL handle");
-    if (!obs_dev) return fail(h, CH_ERR_INVALID, "ch_reset: obs is NULL");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    if (h->rsize == sizeof(double)) {
-        StepParams<double> p = params<double>(h);
-        p.reset_mask = mask_dev; p.obs = obs_dev;
-        e = launch_reset(p, h->team, st);
-    } else {
-        StepParams<float> p = params<float>(h);
-        p.reset_mask = mask_dev; p.obs = obs_dev;
-        e = launch_reset(p, h->team, st);
-    }
-    if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_reset launch: ") + hipGetErrorString(e));
-    if (!mask_dev) h->obs_zero_ptr = obs_dev;                    // every block written in full
-    else if (h->obs_zero_ptr != obs_dev) h->obs_zero_ptr = nullptr;   // some blocks of obs_dev unknown
-    return mask_dev ? CH_OK : clear_error_word(h, st, "ch_reset");
-}
+}  // extern "C"
 
-int ch_reset_with(ch_handle* h, const uint8_t* mask_dev, const int32_t* num_drones, const double* cow_vel,
-                  float* obs_dev, void* stream) {
-    if (!h) return fail(nullptr, CH_ERR_INVALID, "ch_reset_with: NULL handle");
-    if (!obs_dev) return fail(h, CH_ERR_INVALID, "ch_reset_with: obs is NULL");
+// ch_reset (`who`, no draws) and ch_reset_with (optional draws from host arrays)
+static int reset_envs(ch_handle* h, const uint8_t* mask_dev, const int32_t* num_drones, const double* cow_vel,
+                      float* obs_dev, void* stream, const std::string& who, bool injected) {
+    if (!h) return fail(nullptr, CH_ERR_INVALID, who + ": NULL handle");
+    if (!obs_dev) return fail(h, CH_ERR_INVALID, who + ": obs is NULL");
     if (num_drones)
         for (int64_t e = 0; e < h->E; ++e)
             if (num_drones[e] < 1 || num_drones[e] > h->NC)
                 return fail(h, CH_ERR_INVALID,
-                            "ch_reset_with: NUM_DRONES " + std::to_string(num_drones[e]) + " outside [1, num_drones] "
+                            who + ": NUM_DRONES " + std::to_string(num_drones[e]) + " outside [1, num_drones] "
                             "(the reference indexes controllers sized by num_drones, BaseRLAviary.py:80)");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -511,23 +479,27 @@ int ch_reset_with(ch_handle* h, const uint8_t* mask_dev, const int32_t* num_dron
         if (!h->rdv) HIP_TRY(h, hipMalloc(&h->rdv, sizeof(double) * h->E * h->M * 2));
         HIP_TRY(h, hipMemcpyAsync(h->rdv, cow_vel, sizeof(double) * h->E * h->M * 2, hipMemcpyHostToDevice, st));
     }
-    hipError_t e;
-    if (h->rsize == sizeof(double)) {
-        StepParams<double> p = params<double>(h);
+    const hipError_t e = with_params(h, [&](auto p) {
         p.reset_mask = mask_dev; p.obs = obs_dev;
         p.reset_n = num_drones ? h->rdn : nullptr; p.reset_vel = cow_vel ? h->rdv : nullptr;
-        e = launch_reset(p, h->team, st);
-    } else {
-        StepParams<float> p = params<float>(h);
-        p.reset_mask = mask_dev; p.obs = obs_dev;
-        p.reset_n = num_drones ? h->rdn : nullptr; p.reset_vel = cow_vel ? h->rdv : nullptr;
-        e = launch_reset(p, h->team, st);
-    }
-    if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_reset_with launch: ") + hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(st));   // the host arrays may be reused as soon as this returns
-    if (!mask_dev) h->obs_zero_ptr = obs_dev;
-    else if (h->obs_zero_ptr != obs_dev) h->obs_zero_ptr = nullptr;
-    return mask_dev ? CH_OK : clear_error_word(h, st, "ch_reset_with");   // as ch_reset
+        return launch_reset(p, h->team, st);
+    });
+    if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, who + " launch: " + hipGetErrorString(e));
+    if (injected) HIP_TRY(h, hipStreamSynchronize(st));   // the host arrays may be reused as soon as this returns
+    if (!mask_dev) h->obs_zero_ptr = obs_dev;                    // every block written in full
+    else if (h->obs_zero_ptr != obs_dev) h->obs_zero_ptr = nullptr;   // some blocks of obs_dev unknown
+    return mask_dev ? CH_OK : clear_error_word(h, st, who.c_str());
+}
+
+extern "C" {
+
+int ch_reset(ch_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
+    return reset_envs(h, mask_dev, nullptr, nullptr, obs_dev, stream, "ch_reset", false);
+}
+
+int ch_reset_with(ch_handle* h, const uint8_t* mask_dev, const int32_t* num_drones, const double* cow_vel,
+                  float* obs_dev, void* stream) {
+    return reset_envs(h, mask_dev, num_drones, cow_vel, obs_dev, stream, "ch_reset_with", true);
 }
 
 }  // extern "C"
@@ -544,10 +516,12 @@ static void fill_step(const ch_handle* h, const ch_step_io* io, P& p) {
 // ch_rollout_collect's fused step (ch_handle.h)
 hipError_t step_actor(ch_handle* h, const ch_step_io* io, hipStream_t st, const MlpArgs& fa, const RolloutArgs& ro,
                       bool launch) {
-    if (h->kernel != 2 || h->rsize != sizeof(double) || h->phase_mask) return hipErrorNotSupported;
+    const StepPlan& pl = h->plan;
+    const int row = pl.actor_row[io->terminal_obs != nullptr];
+    if (row == kStepNoRow) return hipErrorNotSupported;
     StepParams<double> p = params<double>(h);
     fill_step(h, io, p);
-    const hipError_t e = launch_step_v2_actor(p, h->block, h->lds, st, fa, ro, launch);
+    const hipError_t e = launch_step_v2_actor(p, row, pl.block, pl.lds, st, fa, ro, launch);
     if (e == hipSuccess && launch) { h->obs_zero_ptr = io->obs; ++h->ro.fused_steps; }
     return e;
 }
@@ -569,18 +543,14 @@ static int validate_step_io(ch_handle* h, const ch_step_io* io, const char* who)
 
 // one step of a validated io on the handle's device (ch_step; ch_step_n's plain steps)
 static int step_once(ch_handle* h, const ch_step_io* io, hipStream_t st) {
-    hipError_t e;
-    if (h->rsize == sizeof(double)) {
-        StepParams<double> p = params<double>(h);
+    const StepPlan& pl = h->plan;
+    const hipError_t e = with_params(h, [&](auto p) {
         fill_step(h, io, p);
-        e = h->kernel == 2 ? launch_step_v2(p, h->block, h->lds, st) : launch_step(p, h->team, st);
-    } else {
-        StepParams<float> p = params<float>(h);
-        fill_step(h, io, p);
-        e = h->kernel == 2 ? launch_step_v2(p, h->block, h->lds, st) : launch_step(p, h->team, st);
-    }
+        return pl.kernel == 2 ? launch_step_v2(p, pl.step_row[io->terminal_obs != nullptr], pl.block, pl.lds, st)
+                              : launch_step(p, h->team, st);
+    });
     if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_step launch: ") + hipGetErrorString(e));
-    h->obs_zero_ptr = (h->phase_mask & 8) ? nullptr : io->obs;
+    h->obs_zero_ptr = (h->ov.phase_mask & 8) ? nullptr : io->obs;
     // Which buffer holds each env's constant-zero obs bytes is also tracked on the device, per env: the step kernels
     // record the address they wrote (StepParams::obs_tag) and write an env's block in full when the buffer they are
     // given is not that one (k_step2 and k_env compare p.obs_tag[e] with p.obs), so a HIP graph captured on one
@@ -605,53 +575,45 @@ int ch_step_n(ch_handle* h, const ch_step_io* io, int32_t n_steps, void* stream)
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
+    const StepPlan& pl = h->plan;
     // under stream capture: n_steps plain launches (a captured multi-step launch would read the handle's parameter copy
     // as a later call left it, and the upload's host source would not outlive the call)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-    if (cap != hipStreamCaptureStatusNone) {
-        for (int k = 0; k < n_steps; ++k)
-            if ((rc = step_once(h, io, st)) != CH_OK) return rc;
-        return CH_OK;
-    }
     // a buffer whose constant observation bytes are not known to be in place gets one plain step first (it writes
     // them); every step of the multi-step kernel then finds them there
-    if (io->obs != h->obs_zero_ptr || h->kernel != 2 || h->phase_mask) {
+    if (cap == hipStreamCaptureStatusNone && (io->obs != h->obs_zero_ptr || pl.kernel != 2 || h->ov.phase_mask)) {
         if ((rc = step_once(h, io, st)) != CH_OK) return rc;
         done = 1;
     }
-    if (done == n_steps) return CH_OK;
     const int rest = n_steps - done;
-    hipError_t e = hipErrorNotSupported;
-    if (h->kernel == 2 && !h->phase_mask) {
-        // the multi-step kernel reads its parameters from a device copy (k_step2_multi), uploaded when they differ
-        // from the last upload (stream-ordered; a pageable source is staged by the runtime before the call returns)
-        if (!h->d_params) HIP_TRY(h, hipMalloc(&h->d_params, kParamsBytes));
-        auto go = [&](auto p) -> hipError_t {
-            fill_step(h, io, p);
-            using P = decltype(p);
-            static_assert(sizeof(P) <= kParamsBytes, "StepParams fits the device copy");
-            const P* pd = static_cast<const P*>(h->d_params);
-            if (launch_step_v2_multi(p, pd, h->block, h->lds, st, rest, false) != hipSuccess) return hipErrorNotSupported;
-            if (h->params_host.size() != sizeof(P) || std::memcmp(h->params_host.data(), &p, sizeof(P)) != 0) {
-                const hipError_t ce = hipMemcpyAsync(h->d_params, &p, sizeof(P), hipMemcpyHostToDevice, st);
-                if (ce != hipSuccess) return ce;
-                h->params_host.assign(reinterpret_cast<const unsigned char*>(&p),
-                                      reinterpret_cast<const unsigned char*>(&p) + sizeof(P));
-            }
-            return launch_step_v2_multi(p, pd, h->block, h->lds, st, rest);
-        };
-        e = h->rsize == sizeof(double) ? go(params<double>(h)) : go(params<float>(h));
-    }
-    if (e == hipSuccess) {
-        h->multi_steps += rest;
-        h->obs_zero_ptr = io->obs;
+    // the multi-step kernel where the plan has a row for it (and the io asks for no terminal observations); captured,
+    // and at other geometries: one launch per step
+    if (cap != hipStreamCaptureStatusNone || pl.multi_row == kStepNoRow || io->terminal_obs) {
+        for (int k = 0; k < rest; ++k)
+            if ((rc = step_once(h, io, st)) != CH_OK) return rc;
         return CH_OK;
     }
-    if (e != hipErrorNotSupported) return fail(h, CH_ERR_DEVICE, std::string("ch_step_n launch: ") + hipGetErrorString(e));
-    (void)hipGetLastError();
-    for (int k = 0; k < rest; ++k)   // other geometries: one launch per step
-        if ((rc = step_once(h, io, st)) != CH_OK) return rc;
+    if (rest == 0) return CH_OK;
+    // the kernel reads its parameters from a device copy (k_step2_multi), uploaded when they differ from the last
+    // upload (stream-ordered; a pageable source is staged by the runtime before the call returns)
+    if (!h->d_params) HIP_TRY(h, hipMalloc(&h->d_params, kParamsBytes));
+    const hipError_t e = with_params(h, [&](auto p) {
+        fill_step(h, io, p);
+        using P = decltype(p);
+        static_assert(sizeof(P) <= kParamsBytes, "StepParams fits the device copy");
+        if (h->params_host.size() != sizeof(P) || std::memcmp(h->params_host.data(), &p, sizeof(P)) != 0) {
+            const hipError_t ce = hipMemcpyAsync(h->d_params, &p, sizeof(P), hipMemcpyHostToDevice, st);
+            if (ce != hipSuccess) return ce;
+            h->params_host.assign(reinterpret_cast<const unsigned char*>(&p),
+                                  reinterpret_cast<const unsigned char*>(&p) + sizeof(P));
+        }
+        return launch_step_v2_multi(p, static_cast<const P*>(h->d_params), pl.multi_row, pl.multi_block, pl.multi_lds, st,
+                                    rest);
+    });
+    if (e != hipSuccess) return fail(h, CH_ERR_DEVICE, std::string("ch_step_n launch: ") + hipGetErrorString(e));
+    h->multi_steps += rest;
+    h->obs_zero_ptr = io->obs;
     return CH_OK;
 }
 
@@ -740,10 +702,9 @@ int ch__set_debug(ch_handle* h, double* dev) {
 /* Internal diagnostics: step kernel version (1 = team-per-env ch_kernels.hip, 2 = role-split ch_step.hip). */
 int ch__set_kernel(ch_handle* h, int32_t version) {
     if (!h || (version != 1 && version != 2)) return CH_ERR_INVALID;
-    if (version == 2 && h->lds > 160 * 1024) return CH_ERR_UNSUPPORTED;
-    h->kernel = version;
-    HIP_TRY(h, prepare_step(h));
-    return CH_OK;
+    StepOverrides ov = h->ov;
+    ov.kernel = version;
+    return replan(h, ov);
 }
 
 /* Internal diagnostics: device buffer [grid][16] of per-workgroup timestamps written by the v2 kernel. */
@@ -755,34 +716,29 @@ int ch__set_tstamp(ch_handle* h, long long* dev) {
 
 /* Internal diagnostics: override the v2 geometry (envs per workgroup, block size) for sweeps. */
 int ch__set_geometry(ch_handle* h, int32_t G, int32_t block) {
-    if (!h || G < 1 || G > 64 || G * h->NC > 64 || block < 128 || block % 64 ||
-        block > ((h->pw || h->cfg.physics != CH_PHYS_PYB) ? CH_V2_MAX_BLOCK_PW : CH_V2_MAX_BLOCK))
-        return CH_ERR_INVALID;
-    if (G * h->M > 3 * (block - 64)) return CH_ERR_UNSUPPORTED;   // the cow waves prefetch <= 3 spawn slots per lane
-    size_t lds = V2Layout(G, h->NC, h->M, h->P, h->cfg.mode, (int)h->rsize, h->pw ? block / 64 - 1 : 0).bytes();
-    if (lds > 160 * 1024) return CH_ERR_UNSUPPORTED;
-    bool sep = false;
-    if (!h->pw) {
-        const size_t l = V2Layout(G, h->NC, h->M, h->P, h->cfg.mode, (int)h->rsize, 0, true).bytes();
-        if (l <= 160 * 1024) { sep = true; lds = l; }
-    }
-    h->G = G; h->block = block; h->lds = lds; h->sep = sep;
-    HIP_TRY(h, prepare_step(h));
-    return CH_OK;
+    if (!h) return CH_ERR_INVALID;
+    StepOverrides ov = h->ov;
+    ov.geometry = true; ov.G = G; ov.block = block;
+    return replan(h, ov);
 }
 
 /* Internal diagnostics: v2 geometry (envs per workgroup, block size, dynamic LDS bytes). */
 int ch__geometry(const ch_handle* h, int32_t* G, int32_t* block, int64_t* lds, int32_t* kernel) {
     if (!h) return CH_ERR_INVALID;
-    if (G) *G = h->G;
-    if (block) *block = h->block;
-    if (lds) *lds = (int64_t)h->lds;
-    if (kernel) *kernel = h->kernel;
+    if (G) *G = h->plan.G;
+    if (block) *block = h->plan.block;
+    if (lds) *lds = (int64_t)h->plan.lds;
+    if (kernel) *kernel = h->plan.kernel;
     return CH_OK;
 }
 
-/* Internal diagnostics: skip kernel phases (1 drones, 2 flock, 4 task, 8 obs) to attribute time; 128 / 256: cow waves
- * on the drone wave's SIMD take no chunks after / before the drone hand-off (v2 scheduling experiments). */
+/* Internal (tests): the plan the handle holds, as ch__step_plan's out (ch_step_plan.cpp). */
+int ch__step_plan_of(const ch_handle* h, int64_t out[13]) {
+    if (!h || !out) return CH_ERR_INVALID;
+    step_plan_out(h->plan, out);
+    return CH_OK;
+}
+
 /* Internal: forget which obs buffer holds valid constant-zero bytes (the caller wrote into it); the
  * next ch_step writes every obs block in full. */
 int ch__obs_invalidate(ch_handle* h, void* stream) {
@@ -794,10 +750,13 @@ int ch__obs_invalidate(ch_handle* h, void* stream) {
     return CH_OK;
 }
 
+/* Internal diagnostics: skip kernel phases (1 drones, 2 flock, 4 task, 8 obs) to attribute time; 128 / 256: cow waves
+ * on the drone wave's SIMD take no chunks after / before the drone hand-off (v2 scheduling experiments). */
 int ch__set_phase_mask(ch_handle* h, int32_t mask) {
     if (!h) return CH_ERR_INVALID;
-    h->phase_mask = mask;
-    return CH_OK;
+    StepOverrides ov = h->ov;
+    ov.phase_mask = mask;
+    return replan(h, ov);
 }
 
 int ch_metrics(ch_handle* h, double* out, int32_t reset_after, void* stream) {

@@ -3,11 +3,16 @@
 // ch_api_eval.cpp (the on-device evaluate_policy and the DTDE driver's evaluation), ch_api_eval_log.cpp (the device-side
 // evaluator log), ch_api_train_log.cpp (the SB3 and the RLlib training log) and ch_api_norm.cpp (the device-side
 // VecNormalize and the collection under it).
+//
+// What the env step launches is the handle's StepPlan (ch_step_plan.h): ch_create asks the planner once, for the
+// handle's shape on its device; ch__set_kernel, ch__set_geometry and ch__set_phase_mask change the overrides and ask
+// again.  ch_step, ch_step_n and the fused rollout step read the plan and launch its rows; none of them decides anything.
 #pragma once
 #include <string>
 #include <vector>
 
 #include "ch_internal.h"
+#include "ch_step_plan.h"
 
 // ch_rollout_collect's state (ch_api_policy.cpp)
 struct ch_rollout_state {
@@ -67,18 +72,18 @@ struct ch_handle {
     double* spawn = nullptr;
     int n_scen = 0, n_cows = 0;
     double* debug = nullptr;
-    int phase_mask = 0;
     // The obs buffer whose constant-zero bytes (rows >= NUM_DRONES, the action-buffer block, padding)
     // are known to hold zeros: the last one a full-block writer (v1 step, full ch_reset, v2 step with
     // obs_full) wrote.  The v2 step then stores only the entries that change.
     const float* obs_zero_ptr = nullptr;
-    // v2 step kernel (ch_step.hip): envs per workgroup, block size, dynamic LDS, cow-pair list
-    int kernel = 2;
+    // the step's kernels and geometry (ch_step_plan.h): the plan, what it was planned for (the shape is cfg and E; the
+    // device's CU count and LDS budget) and the diagnostics' overrides
+    ch::StepPlan plan{};
+    ch::StepOverrides ov;
+    int cus = 0;
+    size_t lds_budget = 0;
     long long* tstamp = nullptr;
-    int G = 1, block = 64, P = 0;
-    bool pw = false;   // v2 with per-wave env tables (herds of kPwMinCattle cows and more)
-    bool sep = false;  // v2 shared tables with the shepherd terms in their own LDS region
-    size_t lds = 0;
+    int P = 0;                   // cow pairs per env, and their list (v2 step)
     uint16_t* pairs = nullptr;
     int* errw = nullptr;        // device error word (CH_DEVERR_* bits), sticky
     double* evald = nullptr;    // [E][NC] evaluation distances (cfg.eval_metrics)
@@ -127,6 +132,6 @@ int marl_ring_args(ch_handle* h, const ch_marl_ep_ring* ring, const ch_step_io* 
 
 // ch_rollout_collect's fused step (ch_api.cpp; launch_step_v2_actor): the step of `io` with the actor forward `fa` on
 // the observations it writes (fa.x == io->obs) and the sampling epilogue `ro`.  launch = false: hipSuccess iff the
-// handle and the net fit the fused kernel (nothing launched).
+// handle's plan and the net fit the fused kernel (nothing launched).
 hipError_t step_actor(ch_handle* h, const ch_step_io* io, hipStream_t st, const ch::MlpArgs& fa, const ch::RolloutArgs& ro,
                       bool launch);

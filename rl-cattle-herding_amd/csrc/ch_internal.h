@@ -105,6 +105,8 @@ struct Level {
 #ifndef CH_V2_MAX_BLOCK_PW
 #define CH_V2_MAX_BLOCK_PW 512   // per-wave-table and physics-variant kernels: 8 waves (their register use allows 2 per SIMD)
 #endif
+// the CU's LDS (MI355X: 160 KiB): the most dynamic LDS a v2 step kernel opts in to, and the cap of the planner's budget
+constexpr size_t kStepLdsMax = 160 * 1024;
 constexpr int kV2EnvInts = 14;
 constexpr int kV2Flags = 32;         // LDS hand-off counters between the drone wave and the cow waves + work counters
 // W = 0: one alpha pair table for the whole workgroup (4 reals per pair, G*P pairs), reused for the
@@ -375,22 +377,22 @@ extern long long g_mlp_launches[kMlpKernels];   // launches of each kernel since
 
 template <class R> hipError_t launch_step(const StepParams<R>& p, int team, hipStream_t st);
 template <class R> hipError_t launch_reset(const StepParams<R>& p, int team, hipStream_t st);
+// The v2 step's launchers take a row of the kernel table (ch_step_plan.h kStepTable, chosen by step_plan) and launch
+// that instantiation; hipErrorInvalidValue for a row that is not one of the launcher's family and precision.
 // launch = false only performs the once-per-device function-attribute opt-in (at ch_create, so that a
 // step captured into a HIP graph needs no host-side setup)
-template <class R> hipError_t launch_step_v2(const StepParams<R>& p, int block, size_t lds, hipStream_t st,
+template <class R> hipError_t launch_step_v2(const StepParams<R>& p, int row, int block, size_t lds, hipStream_t st,
                                              bool launch = true);
-// ch_step_n: n consecutive steps of the same io in one launch (k_step2_multi), for the BASELINE geometries under PYB
-// without terminal observations; hipErrorNotSupported (nothing launched) elsewhere.  launch = false: the attribute
-// opt-in only.
-// `pd`: a device copy of p (the kernel reads its parameters from it).
-template <class R> hipError_t launch_step_v2_multi(const StepParams<R>& p, const StepParams<R>* pd, int block, size_t lds,
-                                                   hipStream_t st, int n_steps, bool launch = true);
+// ch_step_n: n consecutive steps of the same io in one launch (k_step2_multi); `block` and `lds` are the plan's
+// multi_block and multi_lds.  `pd`: a device copy of p (the kernel reads its parameters from it).
+template <class R> hipError_t launch_step_v2_multi(const StepParams<R>& p, const StepParams<R>* pd, int row, int block,
+                                                   size_t lds, hipStream_t st, int n_steps);
 // ch_rollout_collect's fused step (k_step2_actor): the step of the CTDE 16-env x 4-drone x 16-cattle geometry (f64,
 // CH_V2_MAX_BLOCK threads) followed in each workgroup by the actor forward with the sampling epilogue on the 16
-// observation rows it wrote.  hipErrorNotSupported (nothing launched) when the handle's geometry or the net does not
-// fit it; launch = false checks only.
-template <class R> hipError_t launch_step_v2_actor(const StepParams<R>& p, int block, size_t lds, hipStream_t st,
-                                                   const MlpArgs& a, const RolloutArgs& ro, bool launch = true);
+// observation rows it wrote.  hipErrorNotSupported (nothing launched) when the net does not fit it; launch = false
+// checks only.
+hipError_t launch_step_v2_actor(const StepParams<double>& p, int row, int block, size_t lds, hipStream_t st,
+                                const MlpArgs& a, const RolloutArgs& ro, bool launch = true);
 // k_mlp2's one-tile shape for a fused forward (ch_mlp_plan.cpp): LDS strides and dynamic bytes; false when the net does
 // not fit a 12-wave, one-column-tile-per-wave tile (layers <= 192 wide, first-layer live width <= 1152)
 bool mlp2_fused_tile(const MlpArgs& a, int& lda, int& ldh, size_t& bytes);

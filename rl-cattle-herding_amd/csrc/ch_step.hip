@@ -1,6 +1,6 @@
 // ch_step.hip — the kernels and launchers of the fused env-step, v2: k_step2 and k_step2_actor around step2_body
 // (ch_step_body.h, which holds the design comment; ch_step_sync.h the hand-off primitives, ch_step_flock.h the flock
-// math), the geometry dispatch, and the explicit instantiations.
+// math) and one launcher per row of the kernel table (ch_step_plan.h): which row a handle runs is the planner's choice.
 #include "ch_step_body.h"
 #include "ch_mlp2_dev.h"   // mlp2_body (k_step2_actor)
 
@@ -57,7 +57,7 @@ static hipError_t launch_v2_kernel(const StepParams<R>& p, int block, size_t lds
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step2<R, MODE, GT, NT, MT, PHYS, PW, TOBS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStepLdsMax);
         if (e != hipSuccess) return e;
         attr_set.fetch_or(bit, std::memory_order_relaxed);
     }
@@ -67,35 +67,35 @@ static hipError_t launch_v2_kernel(const StepParams<R>& p, int block, size_t lds
     return hipGetLastError();
 }
 
-// geometry specialisations: the BASELINE configs at their default geometry (ch_api.cpp)
-template <class R>
-hipError_t launch_step_v2(const StepParams<R>& p, int block, size_t lds, hipStream_t st, bool launch) {
-    const int G = p.G, N = p.NC, M = p.M;
-    if (p.physics != CH_PHYS_PYB) {   // physics variants (BaseAviary.py:420-450): runtime-geometry instantiation
-        if (p.mode == 1) return launch_v2_kernel<R, 1, 0, 0, 0, true>(p, block, lds, st, launch);
-        if (G == 16 && N == 4 && M == 16) return launch_v2_kernel<R, 0, 16, 4, 16, true>(p, block, lds, st, launch);   // configs[3]
-        return launch_v2_kernel<R, 0, 0, 0, 0, true>(p, block, lds, st, launch);
-    }
-    if (p.pw) {   // per-wave env tables (herds > 16 cows)
-        if (p.mode == 1 && G == 16 && N == 4 && M == 32)
-            return launch_v2_kernel<R, 1, 16, 4, 32, false, true>(p, block, lds, st, launch);   // configs[4]
-        if (p.mode == 1) return launch_v2_kernel<R, 1, 0, 0, 0, false, true>(p, block, lds, st, launch);
-        return launch_v2_kernel<R, 0, 0, 0, 0, false, true>(p, block, lds, st, launch);
-    }
-    if (p.mode == 1) return launch_v2_kernel<R, 1, 0, 0, 0>(p, block, lds, st, launch);
-    if (G == 8 && N == 4 && M == 16) return launch_v2_kernel<R, 0, 8, 4, 16>(p, block, lds, st, launch);          // configs[3]
-    if (G == 16 && N == 4 && M == 16) {   // configs[3]: terminal observations from their producers (TOBS) when asked for
-        if (!launch) {   // (both instantiations' attribute opt-in at ch_create)
-            const hipError_t e = launch_v2_kernel<R, 0, 16, 4, 16, false, false, true>(p, block, lds, st, false);
-            if (e != hipSuccess) return e;
-        }
-        if (p.terminal_obs) return launch_v2_kernel<R, 0, 16, 4, 16, false, false, true>(p, block, lds, st, launch);
-        return launch_v2_kernel<R, 0, 16, 4, 16>(p, block, lds, st, launch);
-    }
-    if (G == 16 && N == 2 && M == 8) return launch_v2_kernel<R, 0, 16, 2, 8>(p, block, lds, st, launch);          // configs[2]
-    if (G == 4 && N == 2 && M == 8) return launch_v2_kernel<R, 0, 4, 2, 8>(p, block, lds, st, launch);            // configs[1]
-    return launch_v2_kernel<R, 0, 0, 0, 0>(p, block, lds, st, launch);
+// k_step2's launchers, one per row of kStepTable's run for R, in the table's order; each is checked against its row
+template <class R> using StepLauncher = hipError_t (*)(const StepParams<R>&, int, size_t, hipStream_t, bool);
+template <int I, class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW = false, bool TOBS = false>
+constexpr StepLauncher<R> step_entry() {
+    static_assert(step_row_is(step_rows(kStepFamStep, kPrecision<R>, true) + I, kStepFamStep, kPrecision<R>, MODE, GT, NT,
+                              MT, PHYS, PW, TOBS), "the launcher is its table row's instantiation");
+    return &launch_v2_kernel<R, MODE, GT, NT, MT, PHYS, PW, TOBS>;
 }
+template <class R>
+constexpr StepLauncher<R> kStepLaunchers[] = {
+    step_entry<0, R, 1, 0, 0, 0, true>(),           step_entry<1, R, 0, 16, 4, 16, true>(),
+    step_entry<2, R, 0, 0, 0, 0, true>(),           step_entry<3, R, 1, 16, 4, 32, false, true>(),
+    step_entry<4, R, 1, 0, 0, 0, false, true>(),    step_entry<5, R, 0, 0, 0, 0, false, true>(),
+    step_entry<6, R, 1, 0, 0, 0>(),                 step_entry<7, R, 0, 8, 4, 16>(),
+    step_entry<8, R, 0, 16, 4, 16, false, false, true>(), step_entry<9, R, 0, 16, 4, 16>(),
+    step_entry<10, R, 0, 16, 2, 8>(),               step_entry<11, R, 0, 4, 2, 8>(),
+    step_entry<12, R, 0, 0, 0, 0>(),
+};
+static_assert(sizeof(kStepLaunchers<double>) / sizeof(void*) == step_rows(kStepFamStep, CH_PREC_F64) &&
+              sizeof(kStepLaunchers<float>) / sizeof(void*) == step_rows(kStepFamStep, CH_PREC_F32),
+              "one launcher per k_step2 row");
+
+template <class R>
+hipError_t launch_step_v2(const StepParams<R>& p, int row, int block, size_t lds, hipStream_t st, bool launch) {
+    const int i = row - step_rows(kStepFamStep, kPrecision<R>, true);
+    if (i < 0 || i >= step_rows(kStepFamStep, kPrecision<R>)) return hipErrorInvalidValue;
+    return kStepLaunchers<R>[i](p, block, lds, st, launch);
+}
+template hipError_t launch_step_v2<double>(const StepParams<double>&, int, int, size_t, hipStream_t, bool);
 
 template <class R, bool TOBS>
 static hipError_t launch_actor_kernel(const StepParams<R>& p, int block, size_t lds, hipStream_t st, const FusedActor& f,
@@ -117,28 +117,30 @@ static hipError_t launch_actor_kernel(const StepParams<R>& p, int block, size_t 
     return hipGetLastError();
 }
 
-template <class R>
-hipError_t launch_step_v2_actor(const StepParams<R>& p, int block, size_t lds, hipStream_t st, const MlpArgs& a,
-                                const RolloutArgs& ro, bool launch) {
-    if constexpr (sizeof(R) != sizeof(double)) {
-        return hipErrorNotSupported;
-    } else {
-        if (p.physics != CH_PHYS_PYB || p.pw || p.mode != 0 || p.G != 16 || p.NC != 4 || p.M != 16 ||
-            block != CH_V2_MAX_BLOCK || a.rows != p.E)
-            return hipErrorNotSupported;
-        FusedActor f;
-        size_t mb = 0;
-        if (!mlp2_fused_tile(a, f.lda, f.ldh, mb)) return hipErrorNotSupported;
-        f.a = a;
-        // (diagnostics, ch__set_mlp_tstamp: the forward's phase clocks in the buffer's second half, rows [grid, 2 grid),
-        // so that the separate launches of the same collection, which use the first, do not overwrite them)
-        f.a.tstamp = g_mlp_tstamp ? g_mlp_tstamp + 16LL * ((p.E + 15) / 16) : nullptr;
-        f.ro = ro;
-        const size_t l = lds > mb ? lds : mb;
-        if (l > (size_t)kFusedLdsMax) return hipErrorNotSupported;
-        return p.terminal_obs ? launch_actor_kernel<R, true>(p, block, l, st, f, launch)
-                              : launch_actor_kernel<R, false>(p, block, l, st, f, launch);
-    }
+constexpr hipError_t (*kActorLaunchers[])(const StepParams<double>&, int, size_t, hipStream_t, const FusedActor&, bool) = {
+    &launch_actor_kernel<double, false>, &launch_actor_kernel<double, true>};
+static_assert(sizeof(kActorLaunchers) / sizeof(void*) == step_rows(kStepFamActor, CH_PREC_F64) &&
+              step_row_is(step_rows(kStepFamActor, CH_PREC_F64, true), kStepFamActor, CH_PREC_F64, 0, 16, 4, 16, false, false, 0) &&
+              step_row_is(step_rows(kStepFamActor, CH_PREC_F64, true) + 1, kStepFamActor, CH_PREC_F64, 0, 16, 4, 16, false, false, 1),
+              "one launcher per k_step2_actor row: <double, 0, 16, 4, 16, TOBS>");
+
+// the shape's half of the fused step's conditions is the planner's (StepPlan::actor_row); the net's is here
+hipError_t launch_step_v2_actor(const StepParams<double>& p, int row, int block, size_t lds, hipStream_t st,
+                                const MlpArgs& a, const RolloutArgs& ro, bool launch) {
+    const int i = row - step_rows(kStepFamActor, CH_PREC_F64, true);
+    if (i < 0 || i >= step_rows(kStepFamActor, CH_PREC_F64)) return hipErrorInvalidValue;
+    if (a.rows != p.E) return hipErrorNotSupported;
+    FusedActor f;
+    size_t mb = 0;
+    if (!mlp2_fused_tile(a, f.lda, f.ldh, mb)) return hipErrorNotSupported;
+    f.a = a;
+    // (diagnostics, ch__set_mlp_tstamp: the forward's phase clocks in the buffer's second half, rows [grid, 2 grid),
+    // so that the separate launches of the same collection, which use the first, do not overwrite them)
+    f.a.tstamp = g_mlp_tstamp ? g_mlp_tstamp + 16LL * ((p.E + 15) / 16) : nullptr;
+    f.ro = ro;
+    const size_t l = lds > mb ? lds : mb;
+    if (l > (size_t)kFusedLdsMax) return hipErrorNotSupported;
+    return kActorLaunchers[i](p, block, l, st, f, launch);
 }
 
 #ifdef CH_COUNT_SPINS
@@ -152,11 +154,6 @@ extern "C" int ch__spin_counts(unsigned long long* out) {
 }
 #endif
 
-template hipError_t launch_step_v2<double>(const StepParams<double>&, int, size_t, hipStream_t, bool);
-template hipError_t launch_step_v2_actor<double>(const StepParams<double>&, int, size_t, hipStream_t, const MlpArgs&,
-                                                 const RolloutArgs&, bool);
-template hipError_t launch_step_v2_actor<float>(const StepParams<float>&, int, size_t, hipStream_t, const MlpArgs&,
-                                                const RolloutArgs&, bool);
-template hipError_t launch_step_v2<float>(const StepParams<float>&, int, size_t, hipStream_t, bool);
+template hipError_t launch_step_v2<float>(const StepParams<float>&, int, int, size_t, hipStream_t, bool);
 
 }  // namespace ch

@@ -36,25 +36,16 @@ __device__ __forceinline__ void step2_once(const StepParams<R>* p, int salt, int
 // only the bodies after chain k and step k's reset decision, so a second drone wave starts it as soon as R_k is
 // published, while the first still closes the books of step k (reward, metrics, env write-back) -- see V2Pipe and
 // step2_body's ROLE in ch_step_body.h; the counters that replace the barrier between two steps: V2Pipe, ch_step_sync.h.
+// Which instantiation that is, and every instantiation's launch bound (CH_MULTI_MAX_BLOCK, CH_MULTI_PIPE_MAX_BLOCK),
+// are the kernel table's (ch_step_plan.h multi_pipelined, multi_max_block).
 template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, int WPE>
-constexpr bool kMultiPipelined = sizeof(R) == 8 && MODE == 0 && GT == 16 && NT == 4 && MT == 16 && !PHYS && !PW && WPE == 1;
+constexpr bool kMultiPipelined = multi_pipelined(kPrecision<R>, MODE, GT, NT, MT, PHYS, PW, WPE);
 // n consecutive steps in one launch (ch_step_n); `pd`: the step's parameters in device memory
 // WPE: the waves per SIMD the registers are allocated for (4: two workgroups per CU, for grids of more workgroups than
 // CUs -- the f32 mode at 262 144 envs: 395.5 vs 294.4 M env-steps/s; at 4096 envs, one workgroup per CU, the register
 // cap only spills: 261.9 vs 297.2 M, profiles/r06/ab/r6n_*)
-#ifndef CH_MULTI_MAX_BLOCK
-#define CH_MULTI_MAX_BLOCK CH_V2_MAX_BLOCK_PW   // 512 threads: 2 waves per SIMD (A/B)
-#endif
-// The pipelined instantiation's own bound: 2 drone waves + 8 cow waves.  Its step loop compiles to 161 VGPRs and no
-// scratch under this bound too (tools/res_usage.sh), inside the 168 registers of 3 waves per SIMD, and the extra cow
-// waves shorten the cow side, which is that loop's critical path (640 beat 576 beat 512).  The other
-// instantiations take 171 VGPRs, which do not fit 3 waves per SIMD: they keep CH_MULTI_MAX_BLOCK.
-#ifndef CH_MULTI_PIPE_MAX_BLOCK
-#define CH_MULTI_PIPE_MAX_BLOCK 640
-#endif
 template <class R, int MODE, int GT, int NT, int MT, bool PHYS, bool PW, int WPE>
-constexpr int kMultiMaxBlock = kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE> ? CH_MULTI_PIPE_MAX_BLOCK
-                               : PW ? CH_V2_MAX_BLOCK_PW : CH_MULTI_MAX_BLOCK;
+constexpr int kMultiMaxBlock = multi_max_block(kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE>, PW);
 template <class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW = false, int WPE = 1>
 __global__ __launch_bounds__((kMultiMaxBlock<R, MODE, GT, NT, MT, PHYS, PW, WPE>))
 __attribute__((amdgpu_waves_per_eu(WPE)))
@@ -95,78 +86,63 @@ void k_step2_multi(const StepParams<R>* __restrict__ pd, int n_steps) {
     }
 }
 
+// launches row's instantiation with the plan's block (clamped to the launch bound) and LDS (with the pipelined
+// instantiation's hand-off): StepPlan::multi_block, multi_lds
 template <class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW = false, int WPE = 1>
 static hipError_t launch_v2_multi_kernel(const StepParams<R>& p, const StepParams<R>* pd, int block, size_t lds,
-                                         hipStream_t st, int n_steps, bool launch) {
+                                         hipStream_t st, int n_steps) {
     static std::atomic<unsigned long long> attr_set{0};
-    constexpr int max_block = kMultiMaxBlock<R, MODE, GT, NT, MT, PHYS, PW, WPE>;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step2_multi<R, MODE, GT, NT, MT, PHYS, PW, WPE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStepLdsMax);
         if (e != hipSuccess) return e;
         attr_set.fetch_or(bit, std::memory_order_relaxed);
     }
-    if constexpr (kMultiPipelined<R, MODE, GT, NT, MT, PHYS, PW, WPE>) {
-        // two drone waves and at least two cow waves that hold the workgroup's cows (three spawn slots per lane); the
-        // fast reset path (sep); room for the hand-off behind the carve
-        const int blk = block < max_block ? block : max_block;
-        if (blk < 256 || p.G * p.M > 3 * (blk - 128) || !p.sep || lds + V2Pipe<R>::kBytes > 160 * 1024)
-            return hipErrorNotSupported;
-        lds += V2Pipe<R>::kBytes;
-    }
-    if (!launch) return hipSuccess;
+    if (block > kMultiMaxBlock<R, MODE, GT, NT, MT, PHYS, PW, WPE>) return hipErrorInvalidValue;
     dim3 grid((p.E + p.G - 1) / p.G);
-    // The handle's block is clamped to the instantiation's launch bound (kMultiMaxBlock): 8 waves where the step loop
-    // needs the registers of 2 waves per SIMD, 10 for the pipelined instantiation, whose loop fits 3 per SIMD.  The cow
-    // waves share their work out dynamically, so the outputs do not depend on how many of them run.
-    hipLaunchKernelGGL((k_step2_multi<R, MODE, GT, NT, MT, PHYS, PW, WPE>), grid, dim3(block < max_block ? block : max_block),
-                       lds, st, pd, n_steps);
+    hipLaunchKernelGGL((k_step2_multi<R, MODE, GT, NT, MT, PHYS, PW, WPE>), grid, dim3(block), lds, st, pd, n_steps);
     return hipGetLastError();
 }
 
-// ch_step_n's kernel for the BASELINE geometries (PYB, no terminal observations); hipErrorNotSupported elsewhere (the
-// caller then launches ch_step n times)
+// k_step2_multi's launchers, one per row of kStepTable's run for R, in the table's order; each is checked against its row
+template <class R> using MultiLauncher = hipError_t (*)(const StepParams<R>&, const StepParams<R>*, int, size_t, hipStream_t, int);
+template <int I, class R, int MODE, int GT, int NT, int MT, bool PHYS = false, bool PW = false, int WPE = 1>
+constexpr MultiLauncher<R> multi_entry() {
+    constexpr int row = step_rows(kStepFamMulti, kPrecision<R>, true) + I;
+    static_assert(step_row_is(row, kStepFamMulti, kPrecision<R>, MODE, GT, NT, MT, PHYS, PW, WPE) &&
+                      kStepTable[row].max_block == kMultiMaxBlock<R, MODE, GT, NT, MT, PHYS, PW, WPE>,
+                  "the launcher is its table row's instantiation");
+    return &launch_v2_multi_kernel<R, MODE, GT, NT, MT, PHYS, PW, WPE>;
+}
+template <class R> struct MultiLaunchers;   // (static members: emitted for the host only, where they are used)
+template <> struct MultiLaunchers<double> {
+    static constexpr MultiLauncher<double> rows[] = {
+        multi_entry<0, double, 1, 16, 4, 32, false, true>(), multi_entry<1, double, 0, 16, 4, 16>(),
+        multi_entry<2, double, 0, 8, 4, 16>(), multi_entry<3, double, 0, 16, 2, 8>(), multi_entry<4, double, 0, 4, 2, 8>()};
+};
+template <> struct MultiLaunchers<float> {
+    static constexpr MultiLauncher<float> rows[] = {multi_entry<0, float, 0, 16, 4, 16, false, false, 4>(),
+                                                    multi_entry<1, float, 0, 16, 4, 16>()};
+};
+static_assert(sizeof(MultiLaunchers<double>::rows) / sizeof(void*) == step_rows(kStepFamMulti, CH_PREC_F64) &&
+              sizeof(MultiLaunchers<float>::rows) / sizeof(void*) == step_rows(kStepFamMulti, CH_PREC_F32),
+              "one launcher per k_step2_multi row");
+
 template <class R>
-hipError_t launch_step_v2_multi(const StepParams<R>& p, const StepParams<R>* pd, int block, size_t lds, hipStream_t st,
-                                int n_steps, bool launch) {
-    const int G = p.G, N = p.NC, M = p.M;
-    if (p.physics != CH_PHYS_PYB || p.terminal_obs) return hipErrorNotSupported;
-    if constexpr (sizeof(R) == sizeof(double)) {
-        if (p.pw) {
-            if (p.mode == 1 && G == 16 && N == 4 && M == 32)
-                return launch_v2_multi_kernel<R, 1, 16, 4, 32, false, true>(p, pd, block, lds, st, n_steps, launch);   // configs[4]
-            return hipErrorNotSupported;
-        }
-        if (p.mode != 0) return hipErrorNotSupported;
-        if (G == 16 && N == 4 && M == 16) return launch_v2_multi_kernel<R, 0, 16, 4, 16>(p, pd, block, lds, st, n_steps, launch);   // configs[3]
-        if (G == 8 && N == 4 && M == 16) return launch_v2_multi_kernel<R, 0, 8, 4, 16>(p, pd, block, lds, st, n_steps, launch);     // configs[3], 2 per CU
-        if (G == 16 && N == 2 && M == 8) return launch_v2_multi_kernel<R, 0, 16, 2, 8>(p, pd, block, lds, st, n_steps, launch);     // configs[2]
-        if (G == 4 && N == 2 && M == 8) return launch_v2_multi_kernel<R, 0, 4, 2, 8>(p, pd, block, lds, st, n_steps, launch);       // configs[1]
-        return hipErrorNotSupported;
-    } else {
-        if (!p.pw && p.mode == 0 && G == 16 && N == 4 && M == 16) {
-            // two workgroups per CU once the grid has them (more than 256 workgroups); attribute opt-in for both at
-            // ch_create (launch == false)
-            if (!launch) {
-                const hipError_t e = launch_v2_multi_kernel<R, 0, 16, 4, 16, false, false, 4>(p, pd, block, lds, st, n_steps, false);
-                if (e != hipSuccess) return e;
-            }
-            if ((p.E + G - 1) / G > 256)
-                return launch_v2_multi_kernel<R, 0, 16, 4, 16, false, false, 4>(p, pd, block, lds, st, n_steps, launch);
-            return launch_v2_multi_kernel<R, 0, 16, 4, 16>(p, pd, block, lds, st, n_steps, launch);
-        }
-        return hipErrorNotSupported;
-    }
+hipError_t launch_step_v2_multi(const StepParams<R>& p, const StepParams<R>* pd, int row, int block, size_t lds,
+                                hipStream_t st, int n_steps) {
+    const int i = row - step_rows(kStepFamMulti, kPrecision<R>, true);
+    if (i < 0 || i >= step_rows(kStepFamMulti, kPrecision<R>)) return hipErrorInvalidValue;
+    return MultiLaunchers<R>::rows[i](p, pd, block, lds, st, n_steps);
 }
 
-
-template hipError_t launch_step_v2_multi<double>(const StepParams<double>&, const StepParams<double>*, int, size_t,
-                                                 hipStream_t, int, bool);
-template hipError_t launch_step_v2_multi<float>(const StepParams<float>&, const StepParams<float>*, int, size_t,
-                                                hipStream_t, int, bool);
+template hipError_t launch_step_v2_multi<double>(const StepParams<double>&, const StepParams<double>*, int, int, size_t,
+                                                 hipStream_t, int);
+template hipError_t launch_step_v2_multi<float>(const StepParams<float>&, const StepParams<float>*, int, int, size_t,
+                                                hipStream_t, int);
 
 }  // namespace ch

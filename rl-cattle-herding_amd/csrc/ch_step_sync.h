@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ch_internal.h"
+#include "ch_step_plan.h"   // (ch_internal.h; the kernel table and v2_pipe_bytes)
 
 namespace ch {
 
@@ -152,12 +152,12 @@ __device__ __forceinline__ void cow_sync(int* f, int waves, bool global, int* er
 template <class R> struct V2Smem;
 template <class R>
 struct V2Pipe {
-    enum { P_N = 0, P_B, P_C, P_SIMD, P_K = P_SIMD + 2, P_COUNT = 8 };
+    enum { P_N = 0, P_B, P_C, P_SIMD, P_K = P_SIMD + 2, P_COUNT = kPipeCounters };
     static_assert(P_K < P_COUNT, "launch-long counters");
-    static constexpr int kMetG = 16;   // envs per workgroup of the pipelined instantiation
+    static constexpr int kMetG = kPipeMetG;   // envs per workgroup of the pipelined instantiation
     static constexpr int kHoRows = kDroneComps + 1;   // the chain state's rows and kRowEvalDist
-    static constexpr size_t kBytes = (kHoRows + 7) * 64 * sizeof(R) + (size_t)kMetricRows * kMetG * sizeof(double) +
-                                     (2 * 64 + kV2Flags + P_COUNT) * sizeof(int);
+    // (kHoRows + 7) * 64 reals, the metric rows, 2 * 64 + kV2Flags + P_COUNT ints: sized where the planner reads it too
+    static constexpr size_t kBytes = v2_pipe_bytes(sizeof(R));
     R *ho, *d1;
     double* met;
     int *hoi, *flags1, *sync;
