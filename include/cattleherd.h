@@ -835,6 +835,49 @@ int ch_ppo_train_opt(const ch_ppo_net* net, const ch_ppo_hparams* hp, const ch_p
                      const int64_t* idx, int64_t n_idx, int64_t batch_size, float* m, float* v, int64_t* step_dev,
                      float* stats, float* scratch, void* stream);
 
+/* ---- Population update: P independent learners of one architecture in one set of launches ----------------------
+ * Replaces: P independent PPO.train epochs (seeds, hyper-parameter variants), one ch_ppo_train_opt call each; the
+ * reference has no counterpart for running them together.  A minibatch step of one learner is three dependent launches
+ * that fill a small part of the device; here each of the three launches carries every member, the member being a grid
+ * dimension.  A member is everything ch_ppo_train_opt takes: its own weights, Adam state, rollout data, permutation,
+ * hyper-parameters, options with its own stop word, statistics table and scratch.
+ * CONTRACT: after ch_ppo_train_pop every member's weights, m, v, *step_dev, stop word, statistics table and the flat
+ * gradient left in its scratch are bit-for-bit what ch_ppo_train_opt(&net, &hp, &data, &opts, idx, n_idx, batch_size,
+ * m, v, step_dev, stats, scratch, stream) leaves for that member from the same state: the kernels run the same code
+ * on the same arguments, and nothing is shared between members.  The KL gate is per member: one that trips, or whose
+ * stop word is already set, stops exactly as it does alone while the others carry on.
+ * Members may not alias each other's writable memory (weights, m, v, step_dev, stats, scratch, stop word); what is
+ * only read (the data, idx) may be shared. */
+typedef struct ch_ppo_member {
+    ch_ppo_net net; ch_ppo_hparams hp; ch_ppo_data data; ch_ppo_opts opts;
+    const int64_t* idx;          /* [n_idx], this member's permutation */
+    float* m; float* v; int64_t* step_dev;
+    float* stats;                /* [steps][CH_PPO_OPT_STATS], required */
+    float* scratch;              /* ch_ppo_scratch_size(net, batch) floats, 16-byte aligned, the member's own */
+} ch_ppo_member;
+typedef struct ch_ppo_pop ch_ppo_pop;   /* opaque: the kernels' argument tables */
+
+/* Replaces: nothing in the reference (see above).  The object that holds the argument tables of up to max_members
+ * members on `device`: pinned host staging and the device tables, two slots of each, so that a call may fill its
+ * staging while the copy an earlier, still queued call issued reads the other slot's; a slot is reused only after the
+ * event behind its copy.  One object is used from one stream at a time.  CH_ERR_INVALID for max_members < 1 or a NULL
+ * out, CH_ERR_DEVICE / CH_ERR_NOMEM when the allocation fails. */
+int ch_ppo_pop_create(int32_t max_members, int32_t device, ch_ppo_pop** out);
+/* Waits for the copies it issued, then frees the tables.  The caller has let the launches that read them finish. */
+int ch_ppo_pop_destroy(ch_ppo_pop* pop);
+
+/* Replaces: one epoch of PPO.train's minibatch loop for each of n_members independent learners (see above):
+ * ceil(n_idx / batch_size) population steps of three launches each on `stream`, stream-ordered, no host
+ * synchronisation beyond the wait for a staging slot two calls old.  The tables are uploaded once per call; a step
+ * passes its offset into idx and its statistics row as kernel arguments, and a last, partial minibatch has a table of
+ * its own.
+ * Checked on the host before anything is launched: 1 <= n_members <= the object's max_members; every member as
+ * ch_ppo_train_opt checks it, stats required (CH_ERR_INVALID); the members agree on obs_dim, act_dim, the layer counts
+ * and widths, on data.rows and on whether clip_range_vf is set (CH_ERR_UNSUPPORTED).  They may differ in everything
+ * else: every hyper-parameter, clip_range_vf's value, target_kl set or not, which pointers are 16-byte aligned. */
+int ch_ppo_train_pop(ch_ppo_pop* pop, const ch_ppo_member* members, int32_t n_members, int64_t n_idx,
+                     int64_t batch_size, void* stream);
+
 /* Replaces: stable_baselines3.common.utils.explained_variance(rollout_buffer.values.flatten(),
  * rollout_buffer.returns.flatten()), PPO.train's train/explained_variance.  Handle-free; errors through
  * ch_last_error(NULL).  out_dev[0] = 1 - var(returns - values) / var(returns) with population variances (np.var), NaN

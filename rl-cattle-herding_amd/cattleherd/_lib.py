@@ -33,7 +33,8 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_ep_ring_begin", "ch_ep_ring_record", "ch_rollout_collect_log", "ch_ppo_train_log",
            "ch_explained_variance_scratch", "ch_explained_variance", "ch_marl_ep_ring_begin", "ch_marl_ep_ring_record",
            "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log", "ch_ppo_train_opt", "ch_norm_scratch_size",
-           "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward", "ch_rollout_collect_norm")
+           "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward", "ch_rollout_collect_norm",
+           "ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
@@ -53,6 +54,8 @@ CH_PPO_OPT_STATS = 7   # ch_ppo_train_opt's columns: ch_ppo_train_log's six, the
 # the device-side VecNormalize's (cattleherd/vec_normalize.py): likewise
 _NORM_EXPORTS = ("ch_norm_scratch_size", "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward",
                  "ch_rollout_collect_norm")
+# the population update's (cattleherd/ppo_pop.py): likewise
+_PPO_POP_EXPORTS = ("ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -111,6 +114,12 @@ class ChPpoData(ctypes.Structure):
 class ChPpoOpts(ctypes.Structure):
     _fields_ = [("target_kl", ctypes.c_double), ("clip_range_vf", ctypes.c_double), ("old_values", ctypes.c_void_p),
                 ("stop_dev", ctypes.c_void_p)]
+
+
+class ChPpoMember(ctypes.Structure):
+    """One member of ch_ppo_train_pop's population: what ch_ppo_train_opt takes, by value."""
+    _fields_ = [("net", ChPpoNet), ("hp", ChPpoHparams), ("data", ChPpoData), ("opts", ChPpoOpts)] + \
+        [(k, ctypes.c_void_p) for k in ("idx", "m", "v", "step_dev", "stats", "scratch")]
 
 
 class ChMarlPpoNet(ctypes.Structure):
@@ -294,6 +303,14 @@ def lib():
     if hasattr(L, "ch_ppo_train_opt"):
         L.ch_ppo_train_opt.argtypes = [P(ChPpoNet), P(ChPpoHparams), P(ChPpoData), P(ChPpoOpts), vp, i64, i64, vp, vp, vp,
                                        vp, vp, vp]
+    if hasattr(L, "ch_ppo_train_pop"):
+        L.ch_ppo_pop_create.argtypes = [i32, i32, P(vp)]
+        L.ch_ppo_pop_destroy.argtypes = [vp]
+        L.ch_ppo_train_pop.argtypes = [vp, P(ChPpoMember), i32, i64, i64, vp]
+        L.ch__ppo_pop_plan.argtypes = [i32, P(i32 * 3)]
+        L.ch__ppo_pop_plan.restype = ctypes.c_int
+        L.ch__ppo_pop_kernel.argtypes = [i32]
+        L.ch__ppo_pop_kernel.restype = ctypes.c_char_p
     if hasattr(L, "ch_norm_begin"):
         N = P(ChNorm)
         L.ch_norm_scratch_size.argtypes = [i64, i32]
@@ -302,7 +319,7 @@ def lib():
         L.ch_norm_obs_apply.argtypes = [N, vp, i64, vp, vp, vp]
         L.ch_norm_reward.argtypes = [N, vp, vp, vp, i64, vp, vp]
     optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS + _PPO_OPT_EXPORTS + \
-        _NORM_EXPORTS
+        _NORM_EXPORTS + _PPO_POP_EXPORTS
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in optional or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int
@@ -398,6 +415,26 @@ def ppo_plan(flavour, log=False, gate=False, vclip=False, opts=None):
     names = ppo_kernel_table()
     return {"fb": names[out[0]], "dw": names[out[1]], "adam": names[out[2]], "update": int(out[3]),
             "n_stats": int(out[4]), "opts": bool(out[5])}
+
+
+def ppo_pop_kernel_table():
+    """Internal (tests / diagnostics): the names of the population update's kernel table (csrc/ch_ppo.hip
+    kPpoPopTable), one per instantiation."""
+    rows = []
+    while True:
+        name = lib().ch__ppo_pop_kernel(len(rows))
+        if name is None:
+            return rows
+        rows.append(name.decode())
+
+
+def ppo_pop_plan(vclip=False):
+    """Internal (tests / diagnostics): the kernels of one population step (csrc/ch_ppo.h ppo_pop_plan; host only) with
+    the value clip on or off, as a dict of the fb, dw and adam kernels' names."""
+    out = (ctypes.c_int32 * 3)()
+    check(lib().ch__ppo_pop_plan(int(vclip), ctypes.byref(out)))
+    names = ppo_pop_kernel_table()
+    return {"fb": names[out[0]], "dw": names[out[1]], "adam": names[out[2]]}
 
 
 def ppo_last_step():

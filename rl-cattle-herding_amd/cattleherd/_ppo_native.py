@@ -65,6 +65,16 @@ class NativeState:
         self.step_count = torch.zeros(1, dtype=torch.int64, device=model.device)
         self.scratch = None
 
+    def prepare(self, n, batch_size):
+        """The net struct over the parameters' storage as it is now (a .to() or .data = ... moves it), with the scratch
+        sized for minibatches of ``batch_size`` out of ``n`` rows."""
+        import torch
+        net = net_struct(self.fl, self.model)
+        want = getattr(_lib.lib(), self.fl.prefix + "scratch_size")(ctypes.byref(net), min(batch_size, n))
+        if self.scratch is None or self.scratch.numel() < want:
+            self.scratch = torch.empty(want, dtype=torch.float32, device=self.model.device)
+        return net
+
     def train(self, hp, data, n_epochs, n, batch_size, draw, stats=None, log=False, opts=None):
         """``n_epochs`` calls of the flavour's ``*_train`` on the current stream of the model's device, each over the
         ``n`` row indices (int64, on the device) that ``draw()`` returns, in minibatches of ``batch_size``.  ``hp`` and
@@ -76,10 +86,7 @@ class NativeState:
         (launched: with ``opts``' KL gate the later ones may not have run)."""
         import torch
         lib, dev = _lib.lib(), self.model.device
-        net = net_struct(self.fl, self.model)   # the parameters' storage as it is now (a .to() or .data = ... moves it)
-        want = getattr(lib, self.fl.prefix + "scratch_size")(ctypes.byref(net), min(batch_size, n))
-        if self.scratch is None or self.scratch.numel() < want:
-            self.scratch = torch.empty(want, dtype=torch.float32, device=dev)
+        net = self.prepare(n, batch_size)
         # the entry point and what it takes ahead of the row indices
         entry = "train_opt" if opts is not None else "train_log" if log else "train"
         train = getattr(lib, self.fl.prefix + entry)

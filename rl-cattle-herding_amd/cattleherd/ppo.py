@@ -354,7 +354,20 @@ class PPOUpdate:
 
     def _train_native(self, data, n, nb, rb):
         """The same permutations as the torch path, one ch_ppo_train (log_stats: ch_ppo_train_log; with target_kl or
-        clip_range_vf: ch_ppo_train_opt) call per epoch on the current stream."""
+        clip_range_vf: ch_ppo_train_opt) call per epoch on the current stream.  Three parts, of which a population
+        (cattleherd/ppo_pop.py) keeps the first and the last: prepare, launch, finish."""
+        torch = _torch()
+        dev = self.model.device
+        stats, opts = self._native_prepare(data, n, nb, rb)
+        steps = self._native.train(self._hp, ChPpoData(*(t.data_ptr() for t in data), n), self.n_epochs, n,
+                                   self.batch_size, lambda: torch.randperm(n, device=dev, generator=self.gen),
+                                   stats=stats, log=self.log_stats, opts=opts)
+        return self._native_finish(stats, rb, nb, steps)
+
+    def _native_prepare(self, data, n, nb, rb, pop=False):
+        """The rollout's tensors checked, the call's statistics table and its options with the stop word zeroed:
+        ``(stats, opts)``, either None when the update has no use for it.  ``pop``: for ch_ppo_train_pop, which goes
+        through the option kernels for every member -- always a CH_PPO_OPT_STATS table, always an options struct."""
         torch = _torch()
         dev = self.model.device
         old = rb.values.view(n) if self.clip_range_vf is not None else None
@@ -367,11 +380,16 @@ class PPOUpdate:
             self._stop.zero_()   # (stream-ordered, like the launches behind it)
             opts = _lib.ChPpoOpts(self.target_kl or 0.0, self.clip_range_vf or 0.0, None if old is None else old.data_ptr(),
                                   self._stop.data_ptr() if self.target_kl is not None else None)
+        elif pop:
+            stats = torch.zeros((self.n_epochs * nb, _lib.CH_PPO_OPT_STATS), dtype=torch.float32, device=dev)
+            opts = _lib.ChPpoOpts(0.0, 0.0, None, None)
         elif self.log_stats:
             stats = torch.zeros((self.n_epochs * nb, _lib.CH_PPO_LOG_STATS), dtype=torch.float32, device=dev)
-        steps = self._native.train(self._hp, ChPpoData(*(t.data_ptr() for t in data), n), self.n_epochs, n,
-                                   self.batch_size, lambda: torch.randperm(n, device=dev, generator=self.gen),
-                                   stats=stats, log=self.log_stats, opts=opts)
+        return stats, opts
+
+    def _native_finish(self, stats, rb, nb, steps):
+        """The bookkeeping behind the launches of ``steps`` minibatch steps: the log, or what ``n_updates`` and
+        ``last_stats`` will be read from.  Returns ``steps``."""
         self.sgd_steps += steps
         if self.log_stats:
             self._fill_log(stats, rb, nb)

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "ch_handle.h"
 #include "ch_ppo.h"
@@ -261,9 +262,165 @@ int train(TrainKind kind, const typename F::Net* net, const typename F::Hparams*
     return CH_OK;
 }
 
+bool same_arch(const PpoNet& a, const PpoNet& b) {
+    if (a.obs_dim != b.obs_dim || a.act_dim != b.act_dim) return false;
+    for (int ni = 0; ni < 2; ++ni) {
+        if (a.net[ni].layers != b.net[ni].layers) return false;
+        for (int i = 0; i <= a.net[ni].layers; ++i)
+            if (a.net[ni].dims[i] != b.net[ni].dims[i]) return false;
+    }
+    return true;
+}
+
+constexpr int kPopSlots = 2;      // staging and tables a call may fill while an earlier call's copy is still queued
+constexpr int kPopVariants = 2;   // a table for the full minibatches, one for a last, partial minibatch
+
+}  // namespace
+
+// The population's argument tables (see include/cattleherd.h).  A slot is one pinned host block and one device block
+// of the same layout, [variant][fb | dw | adam][max_members], and the event recorded behind the slot's latest copy.
+struct ch_ppo_pop {
+    int max_members = 0, device = 0;
+    size_t bytes = 0;                    // of a slot
+    size_t off[kPopVariants][3] = {};    // the tables' places in it
+    struct Slot { char* host = nullptr; char* dev = nullptr; hipEvent_t copied = nullptr; bool queued = false; } slot[kPopSlots];
+    unsigned calls = 0;
+    PpoPopTables tables(char* base, int variant) const {
+        return {base + off[variant][0], base + off[variant][1], base + off[variant][2]};
+    }
+};
+
+namespace {
+
+int pop_free(ch_ppo_pop* pop) {
+    hipError_t bad = hipSuccess;
+    for (auto& s : pop->slot) {
+        if (s.copied) {
+            if (s.queued) (void)hipEventSynchronize(s.copied);
+            if (hipError_t e = hipEventDestroy(s.copied)) bad = e;
+        }
+        if (s.dev) if (hipError_t e = hipFree(s.dev)) bad = e;
+        if (s.host) if (hipError_t e = hipHostFree(s.host)) bad = e;
+    }
+    delete pop;
+    return bad == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, std::string("ch_ppo_pop_destroy: ") + hipGetErrorString(bad));
+}
+
+// the device current while the object's calls run, the caller's again afterwards
+struct DeviceScope {
+    int prev = -1;
+    hipError_t err;
+    explicit DeviceScope(int device) {
+        err = hipGetDevice(&prev);
+        if (err == hipSuccess && prev != device) err = hipSetDevice(device); else if (err == hipSuccess) prev = -1;
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 }  // namespace
 
 extern "C" {
+
+int ch_ppo_pop_create(int32_t max_members, int32_t device, ch_ppo_pop** out) {
+    const std::string w = "ch_ppo_pop_create: ";
+    if (!out) return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
+    *out = nullptr;
+    if (max_members < 1 || max_members > 65535) return fail(nullptr, CH_ERR_INVALID, w + "max_members must be 1..65535");   // (a grid dimension)
+    DeviceScope scope(device);
+    if (scope.err != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "device: " + hipGetErrorString(scope.err));
+    ch_ppo_pop* pop = new ch_ppo_pop;
+    pop->max_members = max_members; pop->device = device;
+    const PpoPopSizes sz = ppo_pop_entry_sizes();
+    const size_t each[3] = {sz.fb, sz.dw, sz.adam};
+    for (int v = 0; v < kPopVariants; ++v)
+        for (int t = 0; t < 3; ++t) {
+            pop->off[v][t] = pop->bytes;
+            pop->bytes += (each[t] * (size_t)max_members + 255) / 256 * 256;
+        }
+    for (auto& s : pop->slot) {
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&s.host), pop->bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s.dev), pop->bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)pop_free(pop);
+            return fail(nullptr, e == hipErrorOutOfMemory ? CH_ERR_NOMEM : CH_ERR_DEVICE, w + hipGetErrorString(e));
+        }
+    }
+    *out = pop;
+    return CH_OK;
+}
+
+int ch_ppo_pop_destroy(ch_ppo_pop* pop) {
+    if (!pop) return fail(nullptr, CH_ERR_INVALID, "ch_ppo_pop_destroy: NULL argument");
+    DeviceScope scope(pop->device);
+    return pop_free(pop);
+}
+
+int ch_ppo_train_pop(ch_ppo_pop* pop, const ch_ppo_member* members, int32_t n_members, int64_t n_idx, int64_t batch_size,
+                     void* stream) {
+    const std::string w = "ch_ppo_train_pop: ";
+    if (!pop || !members) return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
+    if (n_members < 1 || n_members > pop->max_members)
+        return fail(nullptr, CH_ERR_INVALID, w + "n_members must be 1..max_members (" + std::to_string(pop->max_members) + ")");
+    if (n_idx < 1 || batch_size < 1 || batch_size > kMaxBatch) return fail(nullptr, CH_ERR_INVALID, w + "n_idx >= 1 and batch_size 1..2^24 required");
+    // every member as train<Sb3>(kTrainOpt) checks it, then what the members must agree on; nothing is launched before
+    std::vector<PpoMember> mb((size_t)n_members);
+    for (int i = 0; i < n_members; ++i) {
+        const ch_ppo_member& c = members[i];
+        const std::string wi = w + "member " + std::to_string(i) + ": ";
+        if (!c.idx || !c.m || !c.v || !c.step_dev || !c.scratch || !c.stats) return fail(nullptr, CH_ERR_INVALID, wi + "NULL argument (idx, m, v, step_dev, stats and scratch are required)");
+        if (c.opts.clip_range_vf > 0.0 && !c.opts.old_values) return fail(nullptr, CH_ERR_INVALID, wi + "clip_range_vf > 0 needs old_values");
+        if (c.opts.target_kl > 0.0 && !c.opts.stop_dev) return fail(nullptr, CH_ERR_INVALID, wi + "target_kl > 0 needs stop_dev");
+        PpoMember& m = mb[(size_t)i];
+        std::string err;
+        int rc;
+        if ((rc = to_net<Sb3>(&c.net, true, m.n, err)) || (rc = to_data<Sb3>(&c.data, &c.hp, m.d, err))) return fail(nullptr, rc, wi + err);
+        if (misaligned(c.scratch)) return fail(nullptr, CH_ERR_INVALID, wi + "scratch must be 16-byte aligned");
+        m.hp = Sb3::hp(&c.hp);
+        m.o = PpoOpt{c.opts.target_kl, c.opts.clip_range_vf, c.opts.old_values, c.opts.stop_dev};
+        m.idx = reinterpret_cast<const long long*>(c.idx);
+        m.m = c.m; m.v = c.v; m.step_dev = reinterpret_cast<long long*>(c.step_dev);
+        m.stats = c.stats; m.scratch = c.scratch;
+    }
+    for (int i = 1; i < n_members; ++i) {
+        const std::string wi = w + "member " + std::to_string(i) + ": ";
+        if (!same_arch(mb[0].n, mb[(size_t)i].n)) return fail(nullptr, CH_ERR_UNSUPPORTED, wi + "architecture differs from member 0's");
+        if (mb[0].d.rows != mb[(size_t)i].d.rows) return fail(nullptr, CH_ERR_UNSUPPORTED, wi + "data rows differ from member 0's");
+        if ((mb[0].o.clip_range_vf > 0.0) != (mb[(size_t)i].o.clip_range_vf > 0.0))
+            return fail(nullptr, CH_ERR_UNSUPPORTED, wi + "clip_range_vf must be set for every member or for none");
+    }
+    DeviceScope scope(pop->device);
+    if (scope.err != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "device: " + hipGetErrorString(scope.err));
+    hipStream_t st = (hipStream_t)stream;
+    PpoScratch s;
+    ppo_scratch_layout(mb[0].n, std::min(batch_size, n_idx), s);   // one layout for every member and step
+    const int64_t full = std::min(batch_size, n_idx), last = n_idx % full;   // last: the partial minibatch's rows, or 0
+    // the staging slot: not before the copy that read it last is done (two calls ago; the device block behind it is
+    // read by that call's launches, which this call's copy follows in the stream)
+    ch_ppo_pop::Slot& slot = pop->slot[pop->calls++ % kPopSlots];
+    if (slot.queued) {
+        if (hipError_t e = hipEventSynchronize(slot.copied)) return fail(nullptr, CH_ERR_DEVICE, w + "staging: " + hipGetErrorString(e));
+        slot.queued = false;
+    }
+    PpoPopGeom geom[kPopVariants] = {};
+    for (int v = 0; v < (last ? 2 : 1); ++v) {
+        const int64_t batch = v ? last : full;
+        const PpoPopTables host = pop->tables(slot.host, v);
+        for (int i = 0; i < n_members; ++i) ppo_pop_fill(host, i, mb[(size_t)i], batch, ppo_scratch_for(s, batch), &geom[v]);
+    }
+    hipError_t e = hipMemcpyAsync(slot.dev, slot.host, pop->bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(slot.copied, st);
+    if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "tables: " + hipGetErrorString(e));
+    slot.queued = true;
+    const PpoPopPlan p = ppo_pop_plan(mb[0].o.clip_range_vf > 0.0);
+    int64_t k = 0;
+    for (int64_t j = 0; j < n_idx; j += batch_size, ++k) {
+        const int v = n_idx - j < full ? 1 : 0;
+        e = ppo_pop_launch(p, pop->tables(slot.dev, v), geom[v], n_members, j, CH_PPO_OPT_STATS * k, st);
+        if (e != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "launch: " + hipGetErrorString(e));
+    }
+    return CH_OK;
+}
 
 int64_t ch_ppo_param_count(const ch_ppo_net* net) { return param_count<Sb3>(net); }
 int64_t ch_ppo_scratch_size(const ch_ppo_net* net, int64_t batch_size) { return scratch_size<Sb3>(net, batch_size); }
@@ -335,6 +492,16 @@ int ch__ppo_plan(int32_t flavour, int32_t log_stats, int32_t opts, int32_t gate,
 
 // Internal: row `kernel` of the update's kernel table (ch_ppo.hip kPpoTable), its name; NULL past the table.
 const char* ch__ppo_kernel(int32_t kernel) { return ppo_kernel_name(kernel); }
+
+// Internal, host only: ppo_pop_plan (ch_ppo.h) for (value clip on) as out = {fb, dw, adam rows of the population
+// kernels' table}, and row `kernel` of that table (ch_ppo.hip kPpoPopTable), its name; NULL outside the table.
+int ch__ppo_pop_plan(int32_t vclip, int32_t out[3]) {
+    if (!out) return fail(nullptr, CH_ERR_INVALID, "ch__ppo_pop_plan: NULL argument");
+    const PpoPopPlan p = ppo_pop_plan(vclip != 0);
+    out[0] = p.fb; out[1] = p.dw; out[2] = p.adam;
+    return CH_OK;
+}
+const char* ch__ppo_pop_kernel(int32_t kernel) { return ppo_pop_kernel_name(kernel); }
 
 // Internal: the minibatch step launched last in this process (host record, no device work): out = {fb, dw, adam rows,
 // the Adam launch's update bits, its grid}.  ch_*_adam leaves {0, k_ppo_sumsq's row, ...}.

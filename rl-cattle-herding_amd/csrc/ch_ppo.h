@@ -164,4 +164,39 @@ inline hipError_t ppo_launch_stats(const PpoPlan& p, const PpoNet& n, float* scr
     return ppo_launch_adam(p, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, scratch, s, n_partials, batch, stats, st);
 }
 
+// ---- the population update (ch_ppo_train_pop): P members of one architecture in the same three launches ------------
+// The population kernels (ch_ppo.hip kPpoPopTable: one row per instantiation) run ch_ppo_train_opt's bodies on the
+// member that a grid coordinate names -- blockIdx.z of k_ppo_fb_pop, blockIdx.y of k_ppo_dw_pop and k_ppo_adam_pop --
+// with that member's arguments read from a device table instead of the kernel-argument segment.  kPpoTable and
+// g_ppo_last_step know nothing of them.
+enum PpoPopKernel { kPpoPopFb4 = 0, kPpoPopFb5, kPpoPopDw, kPpoPopAdam, kPpoPopKernels };
+const char* ppo_pop_kernel_name(int row);   // NULL outside the table
+
+// the rows of one population step, by (value clip on): pure, like ppo_plan.  The statistics rows are CH_PPO_OPT_STATS
+// wide and the Adam launch's update bits are ppo_plan's for options (3).
+struct PpoPopPlan { int fb, dw, adam; };
+inline PpoPopPlan ppo_pop_plan(bool vclip) { return {vclip ? kPpoPopFb5 : kPpoPopFb4, kPpoPopDw, kPpoPopAdam}; }
+
+// one member as ch_ppo_train_opt would take it
+struct PpoMember {
+    PpoNet n; PpoHp hp; PpoData d; PpoOpt o;
+    const long long* idx;
+    float* m; float* v; long long* step_dev;
+    float* stats;     // the call's first row
+    float* scratch;
+};
+// The three argument tables: arrays, indexed by member, of what k_ppo_{fb,dw,adam}_opt take as kernel arguments (the
+// entries' sizes: ppo_pop_entry_sizes).  A table is written on the host (ppo_pop_fill) and read on the device.
+struct PpoPopTables { void* fb; void* dw; void* adam; };
+struct PpoPopSizes { size_t fb, dw, adam; };
+PpoPopSizes ppo_pop_entry_sizes();
+struct PpoPopGeom { int tiles, dw_grid, adam_grid; };   // the same for every member: it follows from the architecture
+// Member `i`'s entries for minibatches of `batch` rows that start at mb.idx[0] and write mb.stats' first row, built by
+// the code that builds ch_ppo_train_opt's kernel arguments; a step adds its offsets (ppo_pop_launch).
+void ppo_pop_fill(const PpoPopTables& host, int i, const PpoMember& mb, long long batch, const PpoScratch& s, PpoPopGeom* g);
+// one minibatch step of `members` members: rows [idx_off, idx_off + batch) of each member's idx, statistics at
+// stats + stats_off floats
+hipError_t ppo_pop_launch(const PpoPopPlan& p, const PpoPopTables& dev, const PpoPopGeom& g, int members,
+                          long long idx_off, long long stats_off, hipStream_t st);
+
 }  // namespace ch

@@ -29,6 +29,9 @@
 //   k_ppo_adam_opt  |  x + gate |             |             |                |             |
 //   k_ppo_sumsq     no flavour: ch_ppo_adam's sum of squares of a given gradient
 //
+// The population kernels (k_ppo_{fb,dw,adam}_pop, ch_ppo_train_pop: P members per launch, the same bodies over a
+// device table of arguments) follow the solo kernels below and have a table of their own, kPpoPopTable.
+//
 // (k_ppo_dw is the same for a base and its log flavour; k_ppo_adam<kPpoSb3> writes kFbSb3Log's two statistics under a
 // run-time bit of AdamArgs::update.  DESIGN.md 4.12 - 4.14 describe the flavours.)
 //
@@ -233,8 +236,9 @@ struct DwArgs {
 
 // A operand: dz[b][n0 + c]; B operand: act[b][kw0 + 4 c + j] for the j-th accumulator, so register r of accumulator j
 // is dW[n0 + 4 g + r][kw0 + 4 c + j]; bsum: this lane's share of the column sum of dz (the bias gradient)
-template <bool VEC, bool GATHER>
-__device__ __forceinline__ void dw_loop(const DwArgs& a, const DwGemm& G, int n0, int kw0, f32x4 (&acc)[4], float& bsum) {
+// (Args: DwArgs, or the population kernel's view of a table entry)
+template <bool VEC, bool GATHER, class Args>
+__device__ __forceinline__ void dw_loop(const Args& a, const DwGemm& G, int n0, int kw0, f32x4 (&acc)[4], float& bsum) {
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
     const int N = G.N, K = G.K, ncol = min(n0 + c, N - 1);
 #pragma unroll
@@ -330,7 +334,8 @@ __device__ __forceinline__ void tree_sum2(double* sy, double* sd, double y, doub
 // sums over the exactly widened float32 y and v, thread t adding rows t, t + 256, ... and a fixed tree the threads;
 // a one-row minibatch gives 0 / 0 = NaN, which the comparison below keeps (fmax would not).  Everything comes from the
 // scratch region `misc` as k_ppo_fb<kPpoRllibLog> left it: the loss's three coefficients, the tiles' sums, the rows.
-__device__ __forceinline__ void rllib_log_stats(const AdamArgs& a) {
+template <class Args>
+__device__ __forceinline__ void rllib_log_stats(const Args& a) {
     __shared__ double sy[256], sd[256];
     const int tid = threadIdx.x;
     const float* log = a.misc + 4;
@@ -374,6 +379,107 @@ __global__ __launch_bounds__(256) void k_ppo_adam_opt(AdamArgs a, GateArgs gate)
 #include "ch_ppo_adam_body.inc"
 }
 
+// ---- the population kernels (ch_ppo_train_pop) -----------------------------------------------------
+// P members of one architecture in one launch.  A workgroup's member is a grid coordinate -- blockIdx.z of
+// k_ppo_fb_pop, blockIdx.y of the other two; the bodies use blockIdx.x, blockIdx.y (fb) and gridDim.x only -- and its
+// arguments are that member's entry of a device table: the structs k_ppo_*_opt take as kernel arguments, built by the
+// same host code.  The body sees them as `a` through a view, references into the entry (the arrays the bodies index
+// at run time stay in memory, as they stay in the kernel-argument segment) with the step's two offsets added: the
+// minibatch's place in the member's idx, the statistics row.  The table is read-only and `__restrict__`, the member
+// wave-uniform, so the entry's fields come by scalar loads and every branch on them stays uniform.  Members share
+// nothing: each entry points into its member's own weights, moments, scratch, statistics and stop word.
+struct PopFb { FbArgs a; FbOpt o; };
+struct PopDw { DwArgs a; GateArgs gate; };
+struct PopAdam { AdamArgs a; GateArgs gate; };
+
+struct FbView {
+    const PpoNet& n;
+    const PpoData& d;
+    const long long* idx;
+    long long batch;
+    float* scratch;
+    const PpoScratch& s;
+    float clip_range, vf_coef;
+    int normalize, vec_obs;
+    const int (&vec_w)[2][3];
+    float ent_coef, vf_clip, ls_clip;
+    const float* kl_coeff_dev;
+    __device__ FbView(const FbArgs& t, long long idx_off)
+        : n(t.n), d(t.d), idx(t.idx + idx_off), batch(t.batch), scratch(t.scratch), s(t.s), clip_range(t.clip_range),
+          vf_coef(t.vf_coef), normalize(t.normalize), vec_obs(t.vec_obs), vec_w(t.vec_w), ent_coef(t.ent_coef),
+          vf_clip(t.vf_clip), ls_clip(t.ls_clip), kl_coeff_dev(t.kl_coeff_dev) {}
+};
+
+struct DwView {
+    const DwGemm (&g)[6];
+    int ng, wg_ls;
+    const float* obs;
+    const long long* idx;
+    long long batch;
+    int bp, tiles, act_dim;
+    const float* tile_dls;
+    float* g_ls;
+    float ent_coef;
+    float* partial;
+    long long* step_dev;
+    __device__ DwView(const DwArgs& t, long long idx_off)
+        : g(t.g), ng(t.ng), wg_ls(t.wg_ls), obs(t.obs), idx(t.idx + idx_off), batch(t.batch), bp(t.bp), tiles(t.tiles),
+          act_dim(t.act_dim), tile_dls(t.tile_dls), g_ls(t.g_ls), ent_coef(t.ent_coef), partial(t.partial),
+          step_dev(t.step_dev) {}
+};
+
+struct AdamView {
+    const AdamSeg (&seg)[kPpoMaxSeg];
+    int nseg;
+    long long n_params;
+    const float* grad;
+    float* m;
+    float* v;
+    const long long* step_dev;
+    const float* partial;
+    int n_partials;
+    double lr, beta1, beta2, eps, max_grad_norm;
+    float* stats4;
+    const float* tile_stat;
+    const float* misc;
+    int tiles;
+    long long batch;
+    int update;
+    __device__ AdamView(const AdamArgs& t, long long stats_off)   // (the population's statistics are required)
+        : seg(t.seg), nseg(t.nseg), n_params(t.n_params), grad(t.grad), m(t.m), v(t.v), step_dev(t.step_dev),
+          partial(t.partial), n_partials(t.n_partials), lr(t.lr), beta1(t.beta1), beta2(t.beta2), eps(t.eps),
+          max_grad_norm(t.max_grad_norm), stats4(t.stats4 + stats_off), tile_stat(t.tile_stat), misc(t.misc),
+          tiles(t.tiles), batch(t.batch), update(t.update) {}
+};
+
+// F: kFbSb3Opt, kFbSb3OptVf (a later RLlib population is a flavour with options of its own, and a table row)
+template <int F>
+__global__ __launch_bounds__(64 * kFbWaves) void k_ppo_fb_pop(const PopFb* __restrict__ tab, long long idx_off) {
+    const PopFb& e = tab[blockIdx.z];
+    const FbView a(e.a, idx_off);
+    const FbOpt o = e.o;
+#include "ch_ppo_fb_body.inc"
+}
+
+// F: the base flavour, kPpoSb3 (with the gate, as k_ppo_dw_opt)
+template <int F>
+__global__ __launch_bounds__(64 * kDwWaves) void k_ppo_dw_pop(const PopDw* __restrict__ tab, long long idx_off) {
+    using Gate = GateArgs;
+    const PopDw& e = tab[blockIdx.y];
+    const DwView a(e.a, idx_off);
+    const GateArgs gate = e.gate;
+#include "ch_ppo_dw_body.inc"
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_ppo_adam_pop(const PopAdam* __restrict__ tab, long long stats_off) {
+    using Gate = GateArgs;
+    const PopAdam& e = tab[blockIdx.y];
+    const AdamView a(e.a, stats_off);
+    const GateArgs gate = e.gate;
+#include "ch_ppo_adam_body.inc"
+}
+
 int dw_tiles(int n) { return (n + 15) / 16; }
 int dw_kgroups(int k) { return (k + kDwCols - 1) / kDwCols; }
 
@@ -400,13 +506,20 @@ const PpoKernelRow kPpoTable[kPpoKernels] = {   // in PpoKernel's order
     CH_ROW(k_ppo_sumsq, 256),
     CH_ROW(k_ppo_adam<0>, 256), CH_ROW(k_ppo_adam<1>, 256), CH_ROW(k_ppo_adam<3>, 256), CH_ROW(k_ppo_adam_opt, 256),
 };
+// the population kernels' table, by PpoPopKernel
+const PpoKernelRow kPpoPopTable[kPpoPopKernels] = {
+    CH_ROW(k_ppo_fb_pop<4>, 64 * kFbWaves), CH_ROW(k_ppo_fb_pop<5>, 64 * kFbWaves),
+    CH_ROW(k_ppo_dw_pop<0>, 64 * kDwWaves), CH_ROW(k_ppo_adam_pop<0>, 256),
+};
 #undef CH_ROW
 
-// launches row `k` over the kernel's arguments (an option kernel's struct last: a plain kernel does not read it)
-hipError_t launch(int k, dim3 grid, void** args, hipStream_t st) {
-    (void)hipLaunchKernel(kPpoTable[k].fn, grid, dim3(kPpoTable[k].block), args, 0, st);
+hipError_t launch_row(const PpoKernelRow& k, dim3 grid, void** args, hipStream_t st) {
+    (void)hipLaunchKernel(k.fn, grid, dim3(k.block), args, 0, st);
     return hipGetLastError();
 }
+
+// launches row `k` over the kernel's arguments (an option kernel's struct last: a plain kernel does not read it)
+hipError_t launch(int k, dim3 grid, void** args, hipStream_t st) { return launch_row(kPpoTable[k], grid, args, st); }
 
 }  // namespace
 
@@ -481,6 +594,36 @@ GateArgs gate_args(const PpoPlan& p, const PpoOpt* opt, float* scratch, const Pp
     return p.opts ? GateArgs{ppo_stop(*opt), scratch + s.tile_stat, 1.5 * opt->target_kl} : GateArgs{};
 }
 
+// the forward-backward kernel's options (a plain kernel's plan: unused)
+FbOpt fb_opt_args(const PpoPlan& p, const PpoOpt* opt) {
+    return p.opts ? FbOpt{ppo_stop(*opt), opt->old_values, (float)opt->clip_range_vf} : FbOpt{};
+}
+
+// the Adam launch's arguments; returns its grid.  `hp` NULL: the statistics alone, by one workgroup
+unsigned adam_args(AdamArgs& a, const PpoPlan& p, const PpoNet& n, const PpoHp* hp, const float* grad, float* m, float* v,
+                   const long long* step_dev, float* scratch, const PpoScratch& s, int n_partials, long long batch,
+                   float* stats) {
+    std::memset(&a, 0, sizeof(a));
+    for (int ni = 0; ni < 2; ++ni) {
+        const PpoMlp& mlp = n.net[ni];
+        for (int li = 0; li < mlp.layers; ++li) {
+            a.seg[a.nseg++] = AdamSeg{mlp.w[li], mlp.goff_w[li], (long long)mlp.dims[li + 1] * mlp.dims[li]};
+            a.seg[a.nseg++] = AdamSeg{mlp.b[li], mlp.goff_b[li], (long long)mlp.dims[li + 1]};
+        }
+    }
+    if (n.flavour == kPpoSb3) a.seg[a.nseg++] = AdamSeg{n.log_std, n.goff_log_std, (long long)n.act_dim};
+    // by offset, for the kernel's scan (the flat order interleaves the two nets' heads after both MLPs)
+    std::sort(a.seg, a.seg + a.nseg, [](const AdamSeg& x, const AdamSeg& y) { return x.off < y.off; });
+    a.n_params = n.n_params;
+    a.partial = scratch + s.partial; a.n_partials = n_partials;
+    a.stats4 = stats; a.tile_stat = scratch + s.tile_stat; a.misc = scratch + s.misc; a.tiles = s.tiles; a.batch = batch;
+    if (!hp) return 1;
+    a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
+    a.lr = hp->lr; a.beta1 = hp->beta1; a.beta2 = hp->beta2; a.eps = hp->eps; a.max_grad_norm = hp->max_grad_norm;
+    a.update = p.update;
+    return (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
+}
+
 }  // namespace
 
 hipError_t ppo_launch_grad(const PpoPlan& p, const PpoNet& n, const PpoHp& hp, const PpoData& d, const PpoOpt* opt,
@@ -488,7 +631,7 @@ hipError_t ppo_launch_grad(const PpoPlan& p, const PpoNet& n, const PpoHp& hp, c
                            long long* step_dev, int* n_partials, hipStream_t st) {
     FbArgs f;
     fb_args(f, n, hp, d, idx, batch, scratch, s);
-    FbOpt fo = p.opts ? FbOpt{ppo_stop(*opt), opt->old_values, (float)opt->clip_range_vf} : FbOpt{};
+    FbOpt fo = fb_opt_args(p, opt);
     void* fb[] = {&f, &fo};
     g_ppo_last_step.fb = p.fb; g_ppo_last_step.dw = p.dw;
     hipError_t e = launch(p.fb, dim3((unsigned)s.tiles, 2), fb, st);
@@ -517,31 +660,44 @@ hipError_t ppo_launch_adam(const PpoPlan& p, const PpoNet& n, const PpoHp* hp, c
                            float* m, float* v, const long long* step_dev, float* scratch, const PpoScratch& s,
                            int n_partials, long long batch, float* stats, hipStream_t st) {
     AdamArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int ni = 0; ni < 2; ++ni) {
-        const PpoMlp& m = n.net[ni];
-        for (int li = 0; li < m.layers; ++li) {
-            a.seg[a.nseg++] = AdamSeg{m.w[li], m.goff_w[li], (long long)m.dims[li + 1] * m.dims[li]};
-            a.seg[a.nseg++] = AdamSeg{m.b[li], m.goff_b[li], (long long)m.dims[li + 1]};
-        }
-    }
-    if (n.flavour == kPpoSb3) a.seg[a.nseg++] = AdamSeg{n.log_std, n.goff_log_std, (long long)n.act_dim};
-    // by offset, for the kernel's scan (the flat order interleaves the two nets' heads after both MLPs)
-    std::sort(a.seg, a.seg + a.nseg, [](const AdamSeg& x, const AdamSeg& y) { return x.off < y.off; });
-    a.n_params = n.n_params;
-    a.partial = scratch + s.partial; a.n_partials = n_partials;
-    a.stats4 = stats; a.tile_stat = scratch + s.tile_stat; a.misc = scratch + s.misc; a.tiles = s.tiles; a.batch = batch;
-    unsigned grid = 1;
-    if (hp) {
-        a.grad = grad; a.m = m; a.v = v; a.step_dev = step_dev;
-        a.lr = hp->lr; a.beta1 = hp->beta1; a.beta2 = hp->beta2; a.eps = hp->eps; a.max_grad_norm = hp->max_grad_norm;
-        a.update = p.update;
-        grid = (unsigned)std::min<long long>((n.n_params + 1023) / 1024, 512);
-    }
+    const unsigned grid = adam_args(a, p, n, hp, grad, m, v, step_dev, scratch, s, n_partials, batch, stats);
     GateArgs gate = gate_args(p, opt, scratch, s);
     void* args[] = {&a, &gate};
     g_ppo_last_step.adam = p.adam; g_ppo_last_step.update = a.update; g_ppo_last_step.adam_grid = (int)grid;
     return launch(p.adam, dim3(grid), args, st);
+}
+
+const char* ppo_pop_kernel_name(int row) { return row >= 0 && row < kPpoPopKernels ? kPpoPopTable[row].name : nullptr; }
+
+PpoPopSizes ppo_pop_entry_sizes() { return {sizeof(PopFb), sizeof(PopDw), sizeof(PopAdam)}; }
+
+void ppo_pop_fill(const PpoPopTables& host, int i, const PpoMember& mb, long long batch, const PpoScratch& s, PpoPopGeom* g) {
+    // ch_ppo_train_opt's plan (the gate and the clip do not change the arguments' build, only what the options hold)
+    const PpoPlan p = ppo_plan(kPpoSb3, false, true, mb.o.target_kl > 0.0, mb.o.clip_range_vf > 0.0);
+    float* grad = mb.scratch + s.grad;
+    PopFb& f = static_cast<PopFb*>(host.fb)[i];
+    PopDw& w = static_cast<PopDw*>(host.dw)[i];
+    PopAdam& a = static_cast<PopAdam*>(host.adam)[i];
+    fb_args(f.a, mb.n, mb.hp, mb.d, mb.idx, batch, mb.scratch, s);
+    f.o = fb_opt_args(p, &mb.o);
+    g->tiles = s.tiles;
+    g->dw_grid = dw_args(w.a, f.a, mb.n, mb.hp, mb.d, mb.idx, batch, grad, mb.scratch, s, mb.step_dev);
+    w.gate = gate_args(p, &mb.o, mb.scratch, s);
+    g->adam_grid = (int)adam_args(a.a, p, mb.n, &mb.hp, grad, mb.m, mb.v, mb.step_dev, mb.scratch, s, g->dw_grid, batch, mb.stats);
+    a.gate = w.gate;
+}
+
+hipError_t ppo_pop_launch(const PpoPopPlan& p, const PpoPopTables& dev, const PpoPopGeom& g, int members,
+                          long long idx_off, long long stats_off, hipStream_t st) {
+    const unsigned P = (unsigned)members;
+    void* fb[] = {const_cast<void**>(&dev.fb), &idx_off};
+    hipError_t e = launch_row(kPpoPopTable[p.fb], dim3((unsigned)g.tiles, 2, P), fb, st);
+    if (e != hipSuccess) return e;
+    void* dw[] = {const_cast<void**>(&dev.dw), &idx_off};
+    e = launch_row(kPpoPopTable[p.dw], dim3((unsigned)g.dw_grid, P), dw, st);
+    if (e != hipSuccess) return e;
+    void* adam[] = {const_cast<void**>(&dev.adam), &stats_off};
+    return launch_row(kPpoPopTable[p.adam], dim3((unsigned)g.adam_grid, P), adam, st);
 }
 
 }  // namespace ch
