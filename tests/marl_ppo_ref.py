@@ -2,7 +2,14 @@
 seeded synthetic minibatch data, an independent torch restatement of the loss, of the optional global-norm clip +
 Adam step and of the training loop (run in float64 as the reference and in float32 as the yardstick), and the
 project's error measure err(x) = max|x - ref64| / max|ref64| with its acceptance rule
-err(native) <= 4 * max(err(torch32), 32 * 2**-24) (tests/ppo_native_ref.py's, unchanged)."""
+err(native) <= 4 * max(err(torch32), 32 * 2**-24) (tests/ppo_native_ref.py's, unchanged).
+
+Shapes: DRIVER, SMALL and WIDE at the driver's sizes (minibatches of up to 128 rows), and SMALL_ROWS, EDGE_1, EDGE_32
+beyond them (LIMIT_GRAD_CASES, LIMIT_TRAIN_CASE; test_gpu_ppo_limits.py).  check_conditions' margins are narrow enough
+(1e-4 at a ratio edge, a relative 1e-3 at vf_clip_param, 1e-3 at +-log_std_clip) that under make_data's Gaussian noise
+a minibatch of 530 rows expects about 0.1 rows inside one of them, so the index seeds are still found by search on the
+float64 reference and this module needs no gapped noise; ppo_native_ref's SB3 data, whose 1e-3 ratio margin expects
+4.5 such rows at 530, does (ppo_native_ref.gapped_noise)."""
 import math
 import types
 
@@ -37,6 +44,18 @@ GRAD_CASES = [("DRIVER", 128, False), ("DRIVER", 40, False), ("DRIVER", 8, False
 # ch_marl_ppo_train: (rows of the index list, minibatch) -> 6 steps of 128; 4 steps of 48 and one of 32
 TRAIN_CASES = [(768, 128, 6), (224, 48, 5)]
 TRAIN_SEED = 21
+# Beyond the driver's sizes (test_gpu_ppo_limits.py).  SMALL_ROWS: SMALL's net over 1100 rows, a minibatch of 530 -- 34
+# row tiles with 2 rows in the last, two passes of the explained variance's 256-thread loops -- and the 1100 rows in
+# minibatches of 530 (530, 530, 40).  EDGE_1 / EDGE_32: obs_dim 257 (a scalar first layer one column into a second
+# 256-column k-group of the weight gradient), a one-hidden-layer actor, a critic of 240 and 144 (15 and 9 column tiles
+# over 8 waves), the narrowest and the widest head.
+SMALL_ROWS = dict(SMALL, name="SMALL_ROWS", rows=1100, seed=14, idx_seed={(530, False): 1})
+EDGE_1 = dict(name="EDGE_1", obs_dim=257, hiddens=(16,), vf_hiddens=(240, 144), act_dim=1, rows=96, seed=17,
+              idx_seed={(24, False): 1})
+EDGE_32 = dict(EDGE_1, name="EDGE_32", act_dim=32, seed=18)
+LIMIT_GRAD_CASES = [("SMALL_ROWS", 530, False), ("EDGE_1", 24, False), ("EDGE_32", 24, False)]
+LIMIT_TRAIN_CASE = (1100, 530, 3)    # (rows of the index list, minibatch, steps) on SMALL_ROWS
+LIMIT_TRAIN_SEED = 1                 # the permutation's seed, chosen like idx_seed: every step meets check_conditions
 
 
 def hp_for(clamp=False, **kw):

@@ -20,13 +20,13 @@ def sb3_train(model, data, perms, batch_size, target_kl=None, clip_range_vf=None
     """SB3's PPO.train, line by line, over `data` = (obs, actions, old_log_prob, advantages, returns, old_values) and
     one permutation per epoch.  Returns the lists SB3's logger averages, per-minibatch extras and the optimizer:
     dict(pg_losses, value_losses, entropy_losses, clip_fractions, approx_kl_divs, loss, n_epochs_counted,
-    continue_training, steps_applied, vgrad_rows).  max_steps: stop by hand after that many optimizer steps (the
-    "truncated run" a gated one is compared with)."""
+    continue_training, steps_applied, clipped_rows, ratios -- each minibatch's ratios as its step saw them).
+    max_steps: stop by hand after that many optimizer steps (the "truncated run" a gated one is compared with)."""
     obs, actions, old_log_prob, advantages, returns, old_values = data
     n = obs.shape[0]
     opt = opt or torch.optim.Adam(model.parameters(), lr=learning_rate, eps=1e-5)
     out = dict(pg_losses=[], value_losses=[], entropy_losses=[], clip_fractions=[], approx_kl_divs=[], loss=None,
-               n_updates=0, continue_training=True, steps_applied=0, clipped_rows=[], opt=opt)
+               n_updates=0, continue_training=True, steps_applied=0, clipped_rows=[], ratios=[], opt=opt)
     for perm in perms:
         for start in range(0, n, batch_size):
             if max_steps is not None and out["steps_applied"] >= max_steps:
@@ -37,6 +37,7 @@ def sb3_train(model, data, perms, batch_size, target_kl=None, clip_range_vf=None
             if len(adv) > 1:
                 adv = (adv - adv.mean()) / (adv.std() + 1e-8)
             ratio = torch.exp(log_prob - old_log_prob[idx])
+            out["ratios"].append(ratio.detach())
             policy_loss_1 = adv * ratio
             policy_loss_2 = adv * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)
             policy_loss = -torch.min(policy_loss_1, policy_loss_2).mean()

@@ -217,7 +217,8 @@ def test_torch_update_on_a_cpu_buffer_and_no_live_row():
         upd.train(rb)
 
 
-@pytest.mark.parametrize("which,batch,clamp", __import__("marl_ppo_ref").GRAD_CASES)
+@pytest.mark.parametrize("which,batch,clamp", __import__("marl_ppo_ref").GRAD_CASES +
+                         __import__("marl_ppo_ref").LIMIT_GRAD_CASES)
 def test_synthetic_minibatches_meet_the_data_conditions(which, batch, clamp):
     """The GPU tests' inputs, on the float64 reference alone (marl_ppo_ref.check_conditions)."""
     import torch
@@ -245,5 +246,21 @@ def test_training_minibatches_meet_the_data_conditions(n_idx, batch, steps, eps)
     aux, hp = [], R.hp_for(eps=eps)
     stats = R.ref_epoch(m64, R.adam(m64, hp), data64, perm, batch, hp, aux_out=aux)
     assert stats.shape[0] == steps == len(aux)
+    for a, row in zip(aux, stats):
+        R.check_conditions(a, hp, False, row)
+
+
+def test_limit_training_minibatches_meet_the_data_conditions():
+    """SMALL_ROWS's 1100 rows in minibatches of 530 (530, 530 and a partial 40), every step of the float64 run."""
+    import torch
+    import marl_ppo_ref as R
+    shape = R.SMALL_ROWS
+    n_idx, batch, steps = R.LIMIT_TRAIN_CASE
+    data64 = R.make_data(shape, "cpu")
+    m64 = R.make_model(shape, "cpu", torch.float64)
+    perm = torch.randperm(shape["rows"], generator=torch.Generator().manual_seed(R.LIMIT_TRAIN_SEED))[:n_idx]
+    aux, hp = [], R.hp_for(eps=R.TRAIN_EPS)
+    stats = R.ref_epoch(m64, R.adam(m64, hp), data64, perm, batch, hp, aux_out=aux)
+    assert stats.shape[0] == steps == len(aux) and [a["ratio"].numel() for a in aux] == [530, 530, 40]
     for a, row in zip(aux, stats):
         R.check_conditions(a, hp, False, row)

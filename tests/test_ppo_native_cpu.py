@@ -99,10 +99,13 @@ def test_host_only_calls_leave_their_reason():
 
 
 @pytest.mark.parametrize("which,batch", [("DRIVER", 64), ("DRIVER", 40), ("DRIVER", 8), ("DRIVER", 1), ("SMALL", 24),
-                                         ("DENSE", 24), ("DRIVER_DENSE", 40)])
+                                         ("DENSE", 24), ("DRIVER_DENSE", 40)] + __import__("ppo_native_ref").LIMIT_CASES)
 def test_synthetic_minibatches_meet_the_clip_conditions(which, batch):
     """The GPU tests' inputs, on the float64 reference alone: the surrogate really clips, on both edges, and no ratio
-    sits where float32 and float64 could disagree on the branch."""
+    sits where float32 and float64 could disagree on the branch.  The gapped-noise shapes (ppo_native_ref.LIMIT_CASES)
+    keep every ratio 1e-2 away from an edge; their clipped fractions: SMALL_ROWS 0.374 (530 rows) and 0.354 (1030),
+    WIDE 0.500, MANY_WG 0.312, EDGE_A 0.458, EDGE_B 0.333, EDGE_C 0.417."""
+    import numpy as np
     import torch
     import ppo_native_ref as R
     shape = getattr(R, which)
@@ -112,3 +115,29 @@ def test_synthetic_minibatches_meet_the_clip_conditions(which, batch):
     R.check_clip_conditions(ratio, clipped)
     assert torch.isfinite(stats).all()
     assert (data64[3] > 0).any() and (data64[3] < 0).any()
+    if shape.get("gapped"):
+        r = ratio.numpy()
+        print(f"{which} B={batch}: clipped fraction {float(clipped.double().mean()):.3f}")
+        assert min(np.abs(r - (1 - R.CLIP)).min(), np.abs(r - (1 + R.CLIP)).min()) > 1e-2
+
+
+def test_limit_training_minibatches_meet_the_clip_conditions():
+    """SMALL_ROWS's training sequence (1100 rows in minibatches of 530: 530, 530 and 40 rows) in the float64 reference
+    run of the three steps: the first minibatch meets check_clip_conditions by construction, the later ones -- on
+    weights that one and two Adam steps moved -- keep 20-80 % of their rows clipped and both edges populated; the rows
+    that an update carried to within 1e-3 of an edge are counted (the GPU test's clip_fraction allows exactly those)."""
+    import numpy as np
+    import torch
+    import ppo_native_ref as R
+    import train_log_ref as T
+    shape = R.SMALL_ROWS
+    data64 = R.make_data(shape, "cpu")
+    ref = T.update_reference(R.make_model(shape, "cpu", torch.float64), data64, R.limit_train_perm(), R.LIMIT_TRAIN_BATCH, R.HP)
+    assert [r[3].numel() for r in ref] == [530, 530, 40]
+    R.check_clip_conditions(ref[0][3], ref[0][4])
+    for k, (st, akl, count, ratio, clipped) in enumerate(ref):
+        r = ratio.numpy()
+        near = int(((np.abs(r - (1 - R.CLIP)) <= 1e-3) | (np.abs(r - (1 + R.CLIP)) <= 1e-3)).sum())
+        frac = float(clipped.double().mean())
+        print(f"step {k}: clipped {frac:.3f}, clip count {count}, rows within 1e-3 of an edge {near}, approx_kl {float(akl):.5f}")
+        assert torch.isfinite(st).all() and 0.2 <= frac <= 0.8 and (r < 1 - R.CLIP).any() and (r > 1 + R.CLIP).any()
