@@ -49,6 +49,7 @@ import numpy as np
 import pytest
 
 import directed_states as D
+import step_rows as SR
 from helpers import close, oracle_view, stack
 
 pytestmark = pytest.mark.gpu
@@ -102,8 +103,6 @@ def test_directed_step_vs_oracle(case, kernel):
     step, as test_random_rollout_with_autoreset_vs_oracle does): caller actions first, device Philox actions after.
     Flags, resets, actions, counters, level, tally, active, episode and spawn index exact; obs, reward and the state
     to the f64 bars (module docstring).  The first step must put the exact 1 m pair before the device's flock."""
-    import torch
-    import oracle as O
     mode, n, m, level, kw = case
     E = D.E_DIRECTED
     envs, states = D.directed_states(mode, n, m, level, E, D.case_seed(case), _table(m), **kw)
@@ -123,6 +122,22 @@ def test_directed_step_vs_oracle(case, kernel):
         assert (G, lds, kv) == (1, LDS_96[(n, m)], 2), (G, blk, lds, kv)
         assert (blk == 128) == (m > 16)   # per-wave tables: the (1, 128) geometry
     _set_kernel(b, kernel)
+    _steps_vs_oracle(b, envs, states, case)
+    b.close()
+
+
+def _steps_vs_oracle(b, envs, states, case, terminal_obs=True, after_step=None):
+    """The body of test_directed_step_vs_oracle on a handle whose kernel and geometry the caller has set: six lockstep
+    steps with auto-reset from ``states`` (one oracle env per device env), every assertion of that test, the final
+    counts included.  ``after_step(t, pre, acts, dn)``: called once a step has been compared, with the device state
+    before it, the actions it took and the oracle's resets.  Returns the counts of terminations, truncations and
+    resets, and per quantity the worst ratio of error to bar over the run (at most 1 wherever the assertions hold)."""
+    import torch
+    import oracle as O
+    ratio = SR.ratio
+    mode, n, m, level, kw = case
+    E = len(envs)
+    worst_of = dict.fromkeys(("obs", "reward", "drone", "cow_pos", "cow_vel"), 0.0)
     b.reset()
     b.set_state(_device_state(states))
     R, K = b.obs_rows, b.reward_cols
@@ -134,10 +149,10 @@ def test_directed_step_vs_oracle(case, kernel):
             env.set_state(oracle_view(g, e, O.NMAX))
         pre = g
         if t == 0:
-            b.step(torch.tensor(acts0, device=b.device), autoreset=True)
+            b.step(torch.tensor(acts0, device=b.device), autoreset=True, terminal_obs=terminal_obs)
             acts = acts0
         else:
-            b.step(random_actions=True, autoreset=True)
+            b.step(random_actions=True, autoreset=True, terminal_obs=terminal_obs)
             torch.cuda.synchronize()
             acts = b.actions.cpu().numpy()
             for e, env in enumerate(envs):   # (the device draws the live drones' rows)
@@ -154,10 +169,13 @@ def test_directed_step_vs_oracle(case, kernel):
         resets += int(dn.sum())
         terms += int(want_te.any(1).sum())
         truncs += int(want_tr.any(1).sum())
-        ok, worst = close(b.obs.cpu().numpy(), np.stack([r[0] for r in ref]).reshape(E, R, 86), 1e-6, 1e-7)
+        want_o = np.stack([r[0] for r in ref]).reshape(E, R, 86)
+        ok, worst = close(b.obs.cpu().numpy(), want_o, 1e-6, 1e-7)
+        worst_of["obs"] = max(worst_of["obs"], ratio(b.obs.cpu().numpy(), want_o, 1e-6, 1e-7))
         assert ok, (t, worst)
         want_r = np.stack([r[1] for r in ref]).reshape(E, K).astype(np.float32)
         ok, worst = close(b.reward.cpu().numpy(), want_r, 1e-6, 1e-6)
+        worst_of["reward"] = max(worst_of["reward"], ratio(b.reward.cpu().numpy(), want_r, 1e-6, 1e-6))
         assert ok, (t, worst)
         g = b.get_state()
         want = stack([env.get_state() for env in envs])
@@ -169,10 +187,13 @@ def test_directed_step_vs_oracle(case, kernel):
             assert np.array_equal(g["active"][live], want["active"][:, :n][live]), t
         for k in DRONE_KEYS:
             ok, worst = close(g[k][live], want[k][:, :n][live], 1e-9, 1e-12)
+            worst_of["drone"] = max(worst_of["drone"], ratio(g[k][live], want[k][:, :n][live], 1e-9, 1e-12))
             assert ok, (t, k, worst)
         ok, worst = close(g["cow_pos"], want["cow_pos"][:, :m], 1e-12, 1e-13)
+        worst_of["cow_pos"] = max(worst_of["cow_pos"], ratio(g["cow_pos"], want["cow_pos"][:, :m], 1e-12, 1e-13))
         assert ok, (t, worst)
         ok, worst = close(g["cow_vel"], want["cow_vel"][:, :m], 1e-12, 1e-14)
+        worst_of["cow_vel"] = max(worst_of["cow_vel"], ratio(g["cow_vel"], want["cow_vel"][:, :m], 1e-12, 1e-14))
         bad = np.argwhere(~np.isclose(g["cow_vel"], want["cow_vel"][:, :m], rtol=1e-12, atol=1e-14))
         assert ok, (t, worst, [(int(e), D.class_of(int(e)), int(j)) for e, j, _ in bad[:4]])
         if t == 0:
@@ -180,12 +201,14 @@ def test_directed_step_vs_oracle(case, kernel):
             exact = sum(int((D.pair_distances({k: g[k][e] for k in ("n", "drone_pos", "cow_pos")}, m) == 1.0).sum())
                         for e in range(E) if D.flock_runs(states[e]) and not dn[e])
             assert exact >= 1
+        if after_step is not None:
+            after_step(t, pre, acts, dn)
     if level != 7:
         assert terms > 0
     assert truncs > 0
     if mode == 0 or level != 7:   # (a MARL episode ends only when every agent has terminated: never at level 7)
         assert resets > 0
-    b.close()
+    return {"terms": terms, "truncs": truncs, "resets": resets, "worst": worst_of}
 
 
 def _tiled(case, E):
@@ -244,6 +267,12 @@ IDENT = [(C416, "f64", "v1", "v2"), (C432, "f64", "v1", "v2"), ((0, 12, 16, 7, {
          (C416, "f32", ("step_n", (16, 512)), (16, 512))]
 
 
+# ch_step_n's row per (shape, precision, geometry) of IDENT's step_n entries
+STEP_N_ROW = {((0, 4, 16), "f64", (8, 256)): "k_step2_multi<double,0,8,4,16>",
+              ((1, 4, 32), "f64", (16, 512)): "k_step2_multi<double,1,16,4,32,false,true>",
+              ((0, 4, 16), "f32", (16, 512)): "k_step2_multi<float,0,16,4,16>"}
+
+
 @pytest.mark.parametrize("case,prec,first,second", IDENT,
                          ids=[f"{D.case_id(c)}-{p}-{a if isinstance(a, str) else a[0]}-{b}" for c, p, a, b in IDENT])
 def test_directed_kernels_bit_identical(case, prec, first, second):
@@ -252,8 +281,6 @@ def test_directed_kernels_bit_identical(case, prec, first, second):
     geometry against others, ch_step_n's multi-step kernel against single steps.  Outputs, state, metrics and the
     evaluation distances bit for bit.  (The oracle free-running from the same states keeps 5 % of the pairs within
     the predator range through the window: test_directed_free_run_stays_near.)"""
-    import torch
-    from cattleherd import _lib
     mode, n, m, level, kw = case
     E, T = 1001, 40
     s = _tiled(case, E)
@@ -272,34 +299,56 @@ def test_directed_kernels_bit_identical(case, prec, first, second):
         h.reset()
         h.set_state(s)
     if step_n:
-        m0 = _lib.lib().ch__multi_steps(hs[0].handle)
-        hs[0].step_n(T, random_actions=True)
-        later = 0   # auto-resets after the first two steps, counted on the single-step handle
-        for t in range(T):
-            hs[1].step(random_actions=True, autoreset=True, terminal_obs=False)
-            if t >= 2:
-                later += int(hs[1].reset_happened.sum())
-        torch.cuda.synchronize()
-        # the first step after set_state writes every observation block in full (one plain launch), the rest run
-        # inside the multi-step kernel
-        assert _lib.lib().ch__multi_steps(hs[0].handle) - m0 >= T - 1
-        assert _same_outs(_outs(hs[0]), _outs(hs[1]), skip=(4,))   # (no terminal observations from ch_step_n)
+        # the k_step2_multi row the census (tests/step_rows.py HELD) says this case holds, and its plain-step twin
+        held = [SR.held_names(h) for h in hs]
+        assert held[0]["multi_row"] == STEP_N_ROW[(case[:3], prec, first[1])], held[0]
+        assert SR.HELD[held[0]["multi_row"]].endswith(f"[{D.case_id(case)}-{prec}-step_n-{second}]")
+        assert held[1]["step_row"] == held[0]["step_row"] and held[0]["step_row"] in SR.STEP_ROWS
+        later = _step_n_vs_steps(hs, T)
         # the episode counters agree bit for bit below (_same_state), so these resets ran inside the multi-step launch too
         assert later >= 20
     else:
-        resets = 0
-        for t in range(T):
-            outs = []
-            for h in hs:
-                h.step(random_actions=True, autoreset=True, terminal_obs=True)
-                outs.append(_outs(h))
-            torch.cuda.synchronize()
-            assert _same_outs(*outs), t
-            resets += int(outs[0][5].sum())
-        assert resets > 0
+        assert _lockstep(hs, T, terminal_obs=True) > 0
     _same_state(*hs)
     for h in hs:
         h.close()
+
+
+def _step_n_vs_steps(hs, T):
+    """ch_step_n(T) on hs[0] against T ch_step calls on hs[1], device Philox actions with auto-reset: the outputs bit
+    for bit, and T - 1 steps or more inside the multi-step kernel.  Returns the auto-resets after the first two steps,
+    counted on the single-step handle."""
+    import torch
+    from cattleherd import _lib
+    m0 = _lib.lib().ch__multi_steps(hs[0].handle)
+    hs[0].step_n(T, random_actions=True)
+    later = 0
+    for t in range(T):
+        hs[1].step(random_actions=True, autoreset=True, terminal_obs=False)
+        if t >= 2:
+            later += int(hs[1].reset_happened.sum())
+    torch.cuda.synchronize()
+    # the first step after set_state writes every observation block in full (one plain launch), the rest run
+    # inside the multi-step kernel
+    assert _lib.lib().ch__multi_steps(hs[0].handle) - m0 >= T - 1
+    assert _same_outs(_outs(hs[0]), _outs(hs[1]), skip=(4,))   # (no terminal observations from ch_step_n)
+    return later
+
+
+def _lockstep(hs, T, terminal_obs):
+    """T steps of device Philox actions with auto-reset on every handle of ``hs``, the outputs bit for bit after each
+    (the terminal observations only where they were asked for).  Returns the auto-resets."""
+    import torch
+    resets = 0
+    for t in range(T):
+        outs = []
+        for h in hs:
+            h.step(random_actions=True, autoreset=True, terminal_obs=terminal_obs)
+            outs.append(_outs(h))
+        torch.cuda.synchronize()
+        assert _same_outs(*outs, skip=() if terminal_obs else (4,)), t
+        resets += int(outs[0][5].sum())
+    return resets
 
 
 F32_CASES = [(0, 4, 16, 7, {}), (1, 4, 32, 0, {})]

@@ -78,8 +78,15 @@ BUDGET = 1e-4
 def _f32_step(ci):
     """One CH_PREC_F32 step (no auto-reset) from the directed batch and the oracle's step from the same states, with
     the state after it on both sides: computed once per case, shared by the per-class tests, left unchanged."""
+    return _f32_step_of(CASES[ci])
+
+
+def _f32_step_of(case, prepare=None, tobs=False):
+    """_f32_step's work for any directed case; ``prepare(batch)`` runs on the new handle before its reset (a geometry
+    override, an assertion on its plan).  ``tobs``: the step runs with auto-reset and terminal observations (the only
+    way to the kernels that write those); an env that reset is then judged on its terminal observation, reward and
+    flags, and its carried state -- the new episode's -- is replaced by the oracle's, i.e. not judged ("reset")."""
     import torch
-    case = CASES[ci]
     mode, n, m, level, kw = case
     E = D.E_DIRECTED
     envs, states = D.directed_states(mode, n, m, level, E, D.case_seed(case), _table(m), **kw)
@@ -87,6 +94,8 @@ def _f32_step(ci):
     if "min_drones" in bkw:
         bkw["max_drones"] = n
     b = _batch(mode, n, m, E, level, precision="f32", **bkw)
+    if prepare is not None:
+        prepare(b)
     geom = _geometry(b)
     b.reset()
     pre = _device_state(states)
@@ -95,8 +104,11 @@ def _f32_step(ci):
     kept = bool(np.array_equal(back["drone_pos"], pre["drone_pos"][:, :n]) and
                 np.array_equal(back["cow_pos"], pre["cow_pos"][:, :m]))
     acts = D.first_actions(states, n, seed=7)
-    obs, rew, te, tr = b.step(torch.tensor(acts, device=b.device), autoreset=False)
+    obs, rew, te, tr = b.step(torch.tensor(acts, device=b.device), autoreset=tobs, terminal_obs=tobs)
     torch.cuda.synchronize()
+    reset = b.reset_happened.cpu().numpy().astype(bool) if tobs else np.zeros(E, bool)
+    if tobs:
+        obs = torch.where(b.reset_happened.bool()[:, None, None], b.terminal_obs, obs)
     out = tuple(x.cpu().numpy() for x in (obs, rew, te, tr))
     g = b.get_state()
     b.close()
@@ -105,8 +117,13 @@ def _f32_step(ci):
     want = (np.stack([r[0] for r in ref]).reshape(E, R, 86), np.stack([r[1] for r in ref]).reshape(E, K),
             np.stack([r[2] for r in ref]).reshape(E, K), np.stack([r[3] for r in ref]).reshape(E, K))
     ws = stack([env.get_state() for env in envs])
+    if reset.any():   # (tobs) the new episode's state of an env that reset is not judged: the oracle's in its place
+        for k in g:
+            if k in ws:
+                g[k][reset] = ws[k][reset] if g[k].ndim == 1 else ws[k][reset][:, :g[k].shape[1]]
     ro, ties = D.untie_neighbours(out[0], want[0], ws["n"], lambda e: ws["drone_pos"][e])
-    return {"out": out, "want": (ro,) + want[1:], "g": g, "ws": ws, "pre": pre, "geom": geom, "kept": kept, "ties": ties,
+    return {"case": case, "reset": reset, "out": out, "want": (ro,) + want[1:], "g": g, "ws": ws, "pre": pre,
+            "geom": geom, "kept": kept, "ties": ties,
             "tie_classes": sorted({D.class_of(int(e)) for e, i in np.argwhere((ro != want[0]).any(-1))})}
 
 
@@ -354,11 +371,14 @@ def _known_params(table):
 def test_f32_step_flags_and_rewards(ci, cls):
     """Rewards within 1e-4 relative down to 1e-6, terminated and truncated exact, in every env of the class (the
     classes that sit on the hold clock included: D.ON_THRESHOLD)."""
-    d = _f32_step(ci)
+    _check_flags_and_rewards(_f32_step(ci), cls)
+
+
+def _check_flags_and_rewards(d, cls):
     sel = _sel(cls)
     (_, rew, te, tr), (_, rr, rte, rtr) = [[x[sel] for x in d[k]] for k in ("out", "want")]
     ok_r, w_r = _worst(rew, rr, 1e-4, 1e-6)
-    print(f"FLAGS {D.case_id(CASES[ci])}-{cls}: reward worst (index, device, oracle) {w_r}; flags differ in "
+    print(f"FLAGS {D.case_id(d['case'])}-{cls}: reward worst (index, device, oracle) {w_r}; flags differ in "
           f"{int((te.astype(bool) != rte.astype(bool)).sum() + (tr.astype(bool) != rtr.astype(bool)).sum())}")
     assert ok_r, ("reward", cls, w_r)
     assert np.array_equal(te.astype(bool), rte.astype(bool)), cls
@@ -366,9 +386,12 @@ def test_f32_step_flags_and_rewards(ci, cls):
 
 
 def _obs_misses(ci, cls):
+    return _obs_misses_of(_f32_step(ci), cls)
+
+
+def _obs_misses_of(d, cls):
     """Observation columns of the class that miss: "col c" elementwise (1e-4 / 1e-6, the yaw rate aside), "scale c"
     against the column's scale over the batch (1e-4) -> worst (device, oracle) or the ratio."""
-    d = _f32_step(ci)
     sel = _sel(cls)
     o, ro = d["out"][0][sel].astype(np.float64), d["want"][0][sel].astype(np.float64)
     scale = np.maximum(np.abs(d["want"][0]).max(axis=(0, 1)), 1e-6)
@@ -405,7 +428,10 @@ def _rate_misses(o, ro, name):
 
 
 def _step_rate_misses(ci, cls):
-    d = _f32_step(ci)
+    return _step_rate_misses_of(_f32_step(ci), cls)
+
+
+def _step_rate_misses_of(d, cls):
     envs = np.flatnonzero(_sel(cls))
     return _rate_misses(d["out"][0][envs], d["want"][0][envs],
                         lambda ix: f"env {int(envs[ix[0]])} drone {ix[1]} column {7 + ix[2]}")
@@ -448,8 +474,11 @@ def _scale_rule(dev, ref, mask, sel, floor):
 @STEP
 def test_f32_step_integer_state(ci, cls):
     """get_state() after the step: the integer fields and the agents' active bits equal the oracle's."""
-    mode, n, m, level, kw = CASES[ci]
-    d = _f32_step(ci)
+    _check_integer_state(_f32_step(ci), cls)
+
+
+def _check_integer_state(d, cls):
+    mode, n, m, level, kw = d["case"]
     g, ws, sel = d["g"], d["ws"], _sel(cls)
     live = np.arange(n)[None, :] < ws["n"][:, None]
     assert np.array_equal(g["n"], ws["n"])
@@ -459,9 +488,12 @@ def test_f32_step_integer_state(ci, cls):
 
 
 def _state_figures(ci, cls):
+    return _state_figures_of(_f32_step(ci), cls)
+
+
+def _state_figures_of(d, cls):
     """(component, worst ratio against the column's scale, column, device, oracle) of every real component."""
-    mode, n, m, level, kw = CASES[ci]
-    d = _f32_step(ci)
+    mode, n, m, level, kw = d["case"]
     g, ws, pre, sel = d["g"], d["ws"], d["pre"], _sel(cls)
     live = np.arange(n)[None, :] < ws["n"][:, None]
     figs = []

@@ -12,6 +12,7 @@ Tolerances (stated per north_star's fp32 bar, tighter for the fp64 path):
 import numpy as np
 import pytest
 
+import step_rows as SR
 from helpers import close, load, rollout_files, stack, state_at
 
 pytestmark = pytest.mark.gpu
@@ -361,6 +362,16 @@ def test_full_size_properties():
         h.close()
 
 
+# test_step_kernels_v1_v2_bit_identical's default-geometry cases that are production shapes on a 256-CU device:
+# (mode, n, m, E, physics, precision) -> the k_step2 row their steps run (tests/test_step_plan_cpu.py plans the same)
+PRODUCTION_ROWS = {(0, 4, 16, 4096, "pyb", "f64"): "k_step2<double,0,16,4,16,false,false,true>",
+                   (0, 2, 8, 1024, "pyb", "f64"): "k_step2<double,0,16,2,8>",
+                   (1, 4, 32, 4096, "pyb", "f64"): "k_step2<double,1,16,4,32,false,true>",
+                   (0, 4, 16, 4096, "dyn", "f64"): "k_step2<double,0,16,4,16,true>",
+                   (0, 4, 16, 4096, "pyb_gnd_drag_dw", "f64"): "k_step2<double,0,16,4,16,true>",
+                   (0, 4, 16, 4096, "pyb", "f32"): "k_step2<float,0,16,4,16,false,false,true>"}
+
+
 @pytest.mark.parametrize("mode,n,m,E,geom", [(0, 4, 16, 4096, None), (0, 2, 8, 1024, None), (1, 4, 32, 600, None),
                                              (0, 12, 16, 300, None), (1, 3, 8, 257, None), (0, 8, 64, 40, None),
                                              (0, 4, 16, 1000, (4, 128)), (0, 4, 16, 999, (2, 128)),
@@ -392,6 +403,10 @@ def test_step_kernels_v1_v2_bit_identical(mode, n, m, E, geom):
     assert _lib.lib().ch__set_kernel(hs[1].handle, ctypes.c_int32(2)) == 0
     if geom is not None:
         assert _lib.lib().ch__set_geometry(hs[1].handle, ctypes.c_int32(geom[0]), ctypes.c_int32(geom[1])) == 0
+    row = PRODUCTION_ROWS.get((mode, n, m, E, physics, precision))
+    if geom is None and row is not None and SR.device_limits()[0] == 256:
+        # a production shape at its default geometry: the body compiled for it (the steps ask for terminal observations)
+        assert SR.held_names(hs[1])["step_row_tobs"] == row, SR.held_names(hs[1])
     for h in hs:
         h.reset()
     for t in range(150):

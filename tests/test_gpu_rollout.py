@@ -214,6 +214,7 @@ def test_fused_step_actor_is_bit_identical(T):
     kernel is the one that ran (T - 1 fused steps per collection)."""
     import ctypes
     import torch
+    import step_rows as SR
     from cattleherd import _lib
     from cattleherd.env import HerdBatch
     from cattleherd.policy import DevicePolicy
@@ -225,6 +226,12 @@ def test_fused_step_actor_is_bit_identical(T):
     bufs = []
     for path in (8, 4):
         b = HerdBatch(E, n, m, mode="ctde", curriculum_level=2)
+        if SR.device_limits()[0] == 256:
+            # the plan carries k_step2_actor's two rows (both or neither: `fused_actor`) beside configs[3]'s step rows,
+            # which the unfused path launches; tests/step_rows.py names this test as the one that holds the actor rows
+            assert _lib.step_plan_of(b.handle)["fused_actor"] == 1 and set(SR.ACTOR_ROWS) <= set(_lib.STEP_KERNELS)
+            assert all(SR.HELD[r].endswith("test_fused_step_actor_is_bit_identical") for r in SR.ACTOR_ROWS)
+            assert SR.held_names(b)["step_row"] == "k_step2<double,0,16,4,16>"
         b.reset()
         b.set_state({"step_counter": sc})
         assert L.ch__set_rollout_path(b.handle, ctypes.c_int32(path)) == 0

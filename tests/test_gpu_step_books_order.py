@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 
 import directed_states as D
+import step_rows as SR
 from helpers import stack
 
 LEVEL = 0
@@ -124,6 +125,10 @@ def test_schedule_on_oracle(steps):
     _ended_schedule(ended, steps)
 
 
+# ch_step_n's row per geometry of this file: the pipelined one, none under its minimum block, the unpipelined 8-env one
+MULTI_ROW = {(16, 512): "k_step2_multi<double,0,16,4,16>", (16, 192): None, (8, 512): "k_step2_multi<double,0,8,4,16>"}
+
+
 def _pair(E, geom, **kw):
     from cattleherd import _lib
     from cattleherd.env import HerdBatch
@@ -131,6 +136,8 @@ def _pair(E, geom, **kw):
     hs = [HerdBatch(E, N, M, mode="ctde", curriculum_level=LEVEL, max_drones=N, **kw) for _ in range(2)]
     # the first handle runs ch_step_n on the multi-step kernel's geometry, the second plain steps on the default one
     assert _lib.lib().ch__set_geometry(hs[0].handle, ctypes.c_int32(geom[0]), ctypes.c_int32(geom[1])) == 0
+    assert SR.held_names(hs[0])["multi_row"] == MULTI_ROW[geom], (geom, SR.held_names(hs[0]))
+    assert SR.held_names(hs[0])["step_row"] == f"k_step2<double,0,{geom[0]},4,16>"
     return hs
 
 

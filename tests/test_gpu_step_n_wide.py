@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import directed_states as D
+import step_rows as SR
 from helpers import stack
 from test_gpu_step_n_pipeline import (LEVEL, M, N, RESET_CASES, SIZES, STEPS, _actions, _assert_same, _check_positions,
                                       _multi, _reset_states)
@@ -33,6 +34,9 @@ def _pair(E, geom, **kw):
     from cattleherd.env import HerdBatch
     hs = [HerdBatch(E, N, M, mode="ctde", **kw) for _ in range(2)]
     assert _lib.lib().ch__set_geometry(hs[0].handle, ctypes.c_int32(geom[0]), ctypes.c_int32(geom[1])) == 0
+    # every shape of this file keeps ch_step_n on the pipelined row, with the 16 x 4 x 16 body for its plain first step
+    assert SR.held_names(hs[0]) == {"step_row": "k_step2<double,0,16,4,16>", "multi_row": "k_step2_multi<double,0,16,4,16>",
+                                    "step_row_tobs": "k_step2<double,0,16,4,16,false,false,true>"}
     return hs
 
 

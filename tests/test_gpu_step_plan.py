@@ -4,11 +4,10 @@ and ch_step_n runs its multi-step kernel exactly where the plan has a row for it
 drawn actions, raw state and metrics of the same number of ch_step calls, bit for bit.
 """
 import ctypes
-import importlib.util
-import os
 
 import pytest
 
+from step_rows import device_limits
 from test_gpu_step_n_pipeline import _assert_same, _multi
 
 pytestmark = pytest.mark.gpu
@@ -22,14 +21,6 @@ SHAPES = [(mode, n, m, F64, E) for mode, n, m in (("ctde", 4, 16), ("ctde", 2, 8
 HAS_MULTI = {s: s[4] == 4096 for s in SHAPES}
 
 
-def _device_limits():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("step_geometry_dump", os.path.join(root, "tools", "step_geometry_dump.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.device_limits()
-
-
 def _batch(mode, n, m, prec, E):
     from cattleherd.env import HerdBatch
     return HerdBatch(E, n, m, mode=mode, precision=prec)
@@ -40,7 +31,7 @@ def test_handle_plan_and_step_n(shape):
     from cattleherd import _lib
     mode, n, m, prec, E = shape
     a = _batch(*shape)
-    cus, lds = _device_limits()   # (after torch has initialised the runtime)
+    cus, lds = device_limits()   # (after torch has initialised the runtime)
     held = _lib.step_plan_of(a.handle)
     want = _lib.step_plan({"ctde": 0, "marl": 1}[mode], n, m, {F64: 0, F32: 1}[prec], 0, E, cus, min(lds, 160 * 1024))
     assert held == want

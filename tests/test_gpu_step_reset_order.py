@@ -28,6 +28,7 @@ import numpy as np
 import pytest
 
 import directed_states as D
+import step_rows as SR
 from helpers import close, oracle_view, stack
 
 LEVEL = 0
@@ -130,6 +131,13 @@ def test_delayed_states_on_oracle(mode, n, m, compat):
             assert causes[e] == dict(altitude=False, collision=False, isolated=False, boundary=False, time=True)
 
 
+# ch_step_n's row per (mode, drones, cattle, precision, geometry) of this file
+MULTI_ROW = {(0, 4, 16, "f64", (16, 512)): "k_step2_multi<double,0,16,4,16>",
+             (0, 2, 8, "f64", (16, 512)): "k_step2_multi<double,0,16,2,8>",
+             (0, 4, 16, "f32", (16, 512)): "k_step2_multi<float,0,16,4,16>",
+             (1, 4, 32, "f64", (16, 512)): "k_step2_multi<double,1,16,4,32,false,true>"}
+
+
 def _pair(mode, n, m, E, geom, **kw):
     from cattleherd import _lib
     from cattleherd.env import HerdBatch
@@ -137,6 +145,7 @@ def _pair(mode, n, m, E, geom, **kw):
                     **kw) for _ in range(2)]
     # the first handle runs ch_step_n on the multi-step kernel's geometry, the second plain steps on the default one
     assert _lib.lib().ch__set_geometry(hs[0].handle, ctypes.c_int32(geom[0]), ctypes.c_int32(geom[1])) == 0
+    assert SR.held_names(hs[0])["multi_row"] == MULTI_ROW[(mode, n, m, kw.get("precision", "f64"), geom)], SR.held_names(hs[0])
     return hs
 
 
