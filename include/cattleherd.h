@@ -364,6 +364,52 @@ int ch_rollout_collect(ch_handle* h, const ch_rollout* rb, const ch_rollout_io* 
                        const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
                        int32_t bootstrap_truncated, void* stream);
 
+/* ---- Population collection: P members' policies collect on one env batch ------------------------------------------
+ * Replaces: P calls of ch_rollout_collect, one per member of a population (seeds, hyper-parameter variants) on P handles
+ * of E envs; the reference has no counterpart for running them together.  The envs of a batch are independent and
+ * ch_config.env_id_offset makes env e of a shard global env offset + e, so the members share one handle of P * E envs,
+ * member p owning envs [pE, (p + 1)E): the env step is one launch for everybody, and each of the policy launches carries
+ * every member, the member being a grid dimension.
+ * CONTRACT: after ch_rollout_collect_pop member p's buffers are bit for bit what ch_rollout_collect writes for a handle
+ * of E envs created with the same config and env_id_offset = this handle's + pE, run from the same env state with
+ * member p's actor, critic, log_std, seed, gamma, gae_lambda and the same bootstrap_truncated; the env state of the
+ * slice is that handle's too.  The Philox counter of a sample is (t, action, member-local row) under the member's seed;
+ * last_episode_starts is per member.  Nothing is shared between members but the env step.
+ * `io` is the whole handle's scratch as for ch_rollout_collect (mean [P*E][act_dim], value, terminal_value [P*E],
+ * env_actions [P*E][num_drones][4], the step buffers); member p uses rows [pE, (p + 1)E) of each.  The step writes the
+ * handle's own observation buffer and every step's observation is copied into the members' buffers (the members'
+ * buffers are separate allocations).  The deferred truncation bootstrap has a queue slice and a counter per member and
+ * is flushed with the period of a solo handle of E envs.  ch__set_rollout_path's bits are not read. */
+typedef struct ch_rollout_member {
+    ch_rollout   rb;           /* this member's own buffers, rows = n_envs / n_members */
+    const ch_mlp *actor, *critic;   /* separate nets (no fused actor-critic) */
+    const float* log_std;      /* [act_dim] */
+    uint64_t     seed;
+    float        gamma, gae_lambda;
+} ch_rollout_member;
+typedef struct ch_rollout_pop ch_rollout_pop;   /* opaque: the kernels' argument tables */
+
+/* Replaces: nothing in the reference (see above).  The object that holds the argument tables of up to max_members
+ * members on `device`: one block of entries per launch kind (step forward, flush, last value), in two slots of pinned
+ * host staging and device memory, so that a call may fill its staging while the copy an earlier, still queued call
+ * issued reads the other slot's; a slot is reused only after the event behind its copy.  One object serves one stream
+ * at a time.  CH_ERR_INVALID for max_members outside 1..65535 or a NULL out, CH_ERR_DEVICE / CH_ERR_NOMEM when the
+ * allocation fails. */
+int ch_rollout_pop_create(int32_t max_members, int32_t device, ch_rollout_pop** out);
+/* Waits for the copies it issued, then frees the tables.  The caller has let the launches that read them finish. */
+int ch_rollout_pop_destroy(ch_rollout_pop* pop);
+
+/* The collection (see above), stream-ordered on `stream`, no host synchronisation beyond the wait for a staging slot two
+ * calls old.  The tables are uploaded once per call; the step index is a kernel argument.
+ * Checked on the host before anything is launched (CH_ERR_INVALID unless noted; ch_last_error says which): NULL
+ * arguments; 1 <= n_members <= the object's max_members; the handle's envs divide evenly among the members; a MARL
+ * handle (CH_ERR_UNSUPPORTED); a NULL critic; members that differ from member 0 in architecture (dims, activation, clip,
+ * splits), n_steps or act_dim; nets the forward kernel does not take as one two-segment launch (CH_ERR_UNSUPPORTED:
+ * there is no fallback path here); obs buffers that are not 16-byte aligned; two writable buffer arrays that are the
+ * same pointer. */
+int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
+                           const ch_rollout_io* io, int32_t bootstrap_truncated, void* stream);
+
 /* ---- Device-side SB3 training log: the episode ring (rollout/ep_rew_mean, rollout/ep_len_mean) ---------------
  * Replaces: OnPolicyAlgorithm._update_info_buffer, which appends Monitor's info["episode"] of every env that ended an
  * episode to ep_info_buffer = deque(maxlen=stats_window_size), step by step and in env order inside collect_rollouts;

@@ -34,7 +34,8 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_explained_variance_scratch", "ch_explained_variance", "ch_marl_ep_ring_begin", "ch_marl_ep_ring_record",
            "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log", "ch_ppo_train_opt", "ch_norm_scratch_size",
            "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward", "ch_rollout_collect_norm",
-           "ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop")
+           "ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop", "ch_rollout_pop_create",
+           "ch_rollout_pop_destroy", "ch_rollout_collect_pop")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
@@ -56,6 +57,8 @@ _NORM_EXPORTS = ("ch_norm_scratch_size", "ch_norm_begin", "ch_norm_obs_update", 
                  "ch_rollout_collect_norm")
 # the population update's (cattleherd/ppo_pop.py): likewise
 _PPO_POP_EXPORTS = ("ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop")
+# the population collection's (cattleherd/rollout_pop.py): likewise
+_ROLLOUT_POP_EXPORTS = ("ch_rollout_pop_create", "ch_rollout_pop_destroy", "ch_rollout_collect_pop")
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -319,7 +322,7 @@ def lib():
         L.ch_norm_obs_apply.argtypes = [N, vp, i64, vp, vp, vp]
         L.ch_norm_reward.argtypes = [N, vp, vp, vp, i64, vp, vp]
     optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS + _PPO_OPT_EXPORTS + \
-        _NORM_EXPORTS + _PPO_POP_EXPORTS
+        _NORM_EXPORTS + _PPO_POP_EXPORTS + _ROLLOUT_POP_EXPORTS
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in optional or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int

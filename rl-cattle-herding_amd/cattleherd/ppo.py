@@ -215,7 +215,7 @@ class PPOUpdate:
         return loss
 
     def _flat(self, rb):
-        T, E = rb.T, rb.batch.n_envs
+        T, E = rb.T, rb.obs.shape[1]   # (a population member's buffer has no batch of its own)
         n = T * E
         return (rb.obs.view(n, -1), rb.actions.view(n, -1), rb.log_probs.view(n), rb.advantages.view(n),
                 rb.returns.view(n))

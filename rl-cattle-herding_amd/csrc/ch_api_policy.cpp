@@ -1,11 +1,13 @@
 // ch_api_policy.cpp — the policy half of the C ABI (see include/cattleherd.h): MLP packing and forwards on device
-// buffers (ch_policy.hip), the on-device PPO rollout buffer and its collection loop, the per-agent MARL rollout
-// (ch_aux.hip).  It reaches the env through ch_step and step_actor (ch_api.cpp) and a few fields of the handle.
+// buffers (ch_policy.hip), the on-device PPO rollout buffer and its collection loop, the population's collection
+// (ch_rollout_collect_pop), the per-agent MARL rollout (ch_aux.hip).  It reaches the env through ch_step and step_actor (ch_api.cpp) and a few fields of the handle.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <set>
 #include <string>
+#include <vector>
 
 #include "ch_handle.h"
 
@@ -458,6 +460,310 @@ int ch_rollout_collect_log(ch_handle* h, const ch_rollout* rb, const ch_rollout_
                            int32_t bootstrap_truncated, const ch_ep_ring* ring, void* stream) {
     return rollout_collect(h, rb, io, actor, critic, log_std, seed, gamma, gae_lambda, bootstrap_truncated, ring, stream);
 }
+
+}  // extern "C"
+
+// ---- the population collection (ch_rollout_collect_pop) -------------------------------------------
+namespace {
+constexpr int kRoPopSlots = 2;   // staging and tables a call may fill while an earlier call's copy is still queued
+enum { kRoPopStep = 0, kRoPopFlush, kRoPopLast, kRoPopKinds };   // one block of max_members entries per launch kind
+}  // namespace
+
+// The argument tables (see include/cattleherd.h).  A slot is one pinned host block and one device block of the same
+// layout, [launch kind][max_members] PopMlp entries, and the event recorded behind the slot's latest copy.
+struct ch_rollout_pop {
+    int max_members = 0, device = 0;
+    size_t bytes = 0;                 // of a slot
+    size_t off[kRoPopKinds] = {};     // the blocks' places in it
+    struct Slot { char* host = nullptr; char* dev = nullptr; hipEvent_t copied = nullptr; bool queued = false; } slot[kRoPopSlots];
+    unsigned calls = 0;
+};
+
+namespace {
+
+int ro_pop_free(ch_rollout_pop* pop) {
+    hipError_t bad = hipSuccess;
+    for (auto& s : pop->slot) {
+        if (s.copied) {
+            if (s.queued) (void)hipEventSynchronize(s.copied);
+            if (hipError_t e = hipEventDestroy(s.copied)) bad = e;
+        }
+        if (s.dev) if (hipError_t e = hipFree(s.dev)) bad = e;
+        if (s.host) if (hipError_t e = hipHostFree(s.host)) bad = e;
+    }
+    delete pop;
+    return bad == hipSuccess ? CH_OK : fail(nullptr, CH_ERR_DEVICE, std::string("ch_rollout_pop_destroy: ") + hipGetErrorString(bad));
+}
+
+// the device current while the object is made or freed, the caller's again afterwards
+struct RoPopDevice {
+    int prev = -1;
+    hipError_t err;
+    explicit RoPopDevice(int device) {
+        err = hipGetDevice(&prev);
+        if (err == hipSuccess && prev != device) err = hipSetDevice(device); else if (err == hipSuccess) prev = -1;
+    }
+    ~RoPopDevice() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// ch_rollout_collect's flush period for a handle of E envs: 16 steps, fewer when the queue would pass 1 GiB
+int ro_tv_every(long long E, int obs_dim) {
+    return (int)std::min<long long>(16, std::max<long long>(1, (1LL << 30) / (E * obs_dim * 4)));
+}
+
+// Member p's slice of the handle-wide scratch of a population of P members on n_envs envs: its env count, its first
+// env, and where its rows start in obs / terminal_obs, mean, the one-column arrays (value, terminal_value, reward,
+// terminated, truncated), env_actions (elements) and in the deferred-bootstrap queue (rows; a member's share is the
+// whole queue of a solo handle of E envs)
+struct RoPopSlice { int64_t E, env, obs, mean, row, env_actions, queue; };
+RoPopSlice ro_pop_slice(int64_t n_envs, int P, int p, int obs_dim, int num_drones, int act_dim) {
+    RoPopSlice s;
+    s.E = n_envs / P;
+    s.env = s.E * p;
+    s.obs = s.env * obs_dim;
+    s.mean = s.env * act_dim;
+    s.row = s.env;
+    s.env_actions = s.env * num_drones * 4;
+    s.queue = s.env * ro_tv_every(s.E, obs_dim);
+    return s;
+}
+
+bool same_mlp_arch(const ch_mlp* a, const ch_mlp* b) {
+    if (a->n_layers != b->n_layers || a->hidden_act != b->hidden_act || (a->clip != 0) != (b->clip != 0)) return false;
+    if (a->clip && (a->lo != b->lo || a->hi != b->hi)) return false;
+    if (a->n_layers < 1 || a->n_layers > 4) return true;   // (mlp_args refuses it by name)
+    for (int i = 0; i <= a->n_layers; ++i)
+        if (a->dims[i] != b->dims[i]) return false;
+    for (int i = 0; i < a->n_layers; ++i)
+        if (a->split_out[i] != b->split_out[i] || a->split_in[i] != b->split_in[i]) return false;
+    return true;
+}
+
+bool same_mlp_plan(const MlpPlan& a, const MlpPlan& b) {
+    return a.v2 == b.v2 && a.n == b.n && a.kernel[0] == b.kernel[0] && a.rt == b.rt && a.lda == b.lda && a.ldh == b.ldh &&
+           a.lds == b.lds && a.start[1] == b.start[1] && a.start[2] == b.start[2];
+}
+
+}  // namespace
+
+extern "C" {
+
+int ch_rollout_pop_create(int32_t max_members, int32_t device, ch_rollout_pop** out) {
+    const std::string w = "ch_rollout_pop_create: ";
+    if (!out) return fail(nullptr, CH_ERR_INVALID, w + "NULL argument");
+    *out = nullptr;
+    if (max_members < 1 || max_members > 65535) return fail(nullptr, CH_ERR_INVALID, w + "max_members must be 1..65535");   // (a grid dimension)
+    RoPopDevice scope(device);
+    if (scope.err != hipSuccess) return fail(nullptr, CH_ERR_DEVICE, w + "device: " + hipGetErrorString(scope.err));
+    ch_rollout_pop* pop = new ch_rollout_pop;
+    pop->max_members = max_members; pop->device = device;
+    for (int k = 0; k < kRoPopKinds; ++k) {
+        pop->off[k] = pop->bytes;
+        pop->bytes += (sizeof(PopMlp) * (size_t)max_members + 255) / 256 * 256;
+    }
+    for (auto& s : pop->slot) {
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&s.host), pop->bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s.dev), pop->bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)ro_pop_free(pop);
+            return fail(nullptr, e == hipErrorOutOfMemory ? CH_ERR_NOMEM : CH_ERR_DEVICE, w + hipGetErrorString(e));
+        }
+    }
+    *out = pop;
+    return CH_OK;
+}
+
+int ch_rollout_pop_destroy(ch_rollout_pop* pop) {
+    if (!pop) return fail(nullptr, CH_ERR_INVALID, "ch_rollout_pop_destroy: NULL argument");
+    RoPopDevice scope(pop->device);
+    return ro_pop_free(pop);
+}
+
+/* Internal (tests): where member p's slice starts in each handle-wide scratch array of a collection of n_members
+ * members on n_envs envs of `obs_rows` observation rows and `num_drones` drones (host only): out = {envs per member,
+ * obs / terminal_obs floats, mean floats, value / terminal_value / reward floats, env_actions floats, terminated /
+ * truncated bytes, queue rows}.  The arithmetic ch_rollout_collect_pop uses. */
+int ch__rollout_pop_slice(int64_t n_envs, int32_t n_members, int32_t p, int32_t obs_rows, int32_t num_drones,
+                          int32_t act_dim, int64_t out[7]) {
+    if (!out || n_envs < 1 || n_members < 1 || n_envs % n_members || p < 0 || p >= n_members || obs_rows < 1 ||
+        num_drones < 1 || act_dim < 1)
+        return fail(nullptr, CH_ERR_INVALID, "ch__rollout_pop_slice: bad argument");
+    const RoPopSlice sl = ro_pop_slice(n_envs, n_members, p, obs_rows * 86, num_drones, act_dim);
+    const int64_t v[7] = {sl.E, sl.obs, sl.mean, sl.row, sl.env_actions, sl.row, sl.queue};
+    std::copy(v, v + 7, out);
+    return CH_OK;
+}
+
+int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
+                           const ch_rollout_io* io, int32_t bootstrap_truncated, void* stream) {
+    const std::string w = "ch_rollout_collect_pop: ";
+    if (!h) return fail(nullptr, CH_ERR_INVALID, w + "NULL handle");
+    if (!pop || !members || !io || !io->step) return fail(h, CH_ERR_INVALID, w + "NULL argument");
+    if (n_members < 1 || n_members > pop->max_members)
+        return fail(h, CH_ERR_INVALID, w + "n_members must be 1..max_members (" + std::to_string(pop->max_members) + ")");
+    if (h->cfg.mode != CH_MODE_CTDE) return fail(h, CH_ERR_UNSUPPORTED, w + "the SB3 rollout buffer is for CTDE handles");
+    if (h->E % n_members) return fail(h, CH_ERR_INVALID, w + "the handle's envs must divide evenly among the members");
+    if (pop->device != h->device) return fail(h, CH_ERR_INVALID, w + "the tables are on another device than the handle");
+    const ch_step_io* sio = io->step;
+    if (!io->mean || !io->value || !io->env_actions || !sio->obs || !sio->reward || !sio->terminated || !sio->truncated ||
+        !sio->terminal_obs || !sio->reset_happened || (bootstrap_truncated && !io->terminal_value))
+        return fail(h, CH_ERR_INVALID, w + "NULL argument: mean, value, env_actions, the step buffers (obs, reward, terminated, "
+                                           "truncated, terminal_obs, reset_happened) and terminal_value are required");
+    const int P = n_members;
+    const int64_t E = h->E / P;
+    const ch_rollout_member& m0 = members[0];
+    const int obs_dim = h->rows * 86;
+    // every member as ch_rollout_collect checks it, then what the members must agree on; nothing is launched before
+    std::set<const void*> writable;
+    for (int p = 0; p < P; ++p) {
+        const ch_rollout_member& c = members[p];
+        const ch_rollout& rb = c.rb;
+        const std::string wp = w + "member " + std::to_string(p) + ": ";
+        if (!c.actor || !c.log_std) return fail(h, CH_ERR_INVALID, wp + "NULL argument (actor, log_std)");
+        if (!c.critic) return fail(h, CH_ERR_INVALID, wp + "NULL critic (a fused actor-critic is not supported here)");
+        float* const arrays[9] = {rb.obs, rb.actions, rb.rewards, rb.episode_starts, rb.values, rb.log_probs, rb.advantages,
+                                  rb.returns, rb.last_episode_starts};
+        for (float* a : arrays)
+            if (!a) return fail(h, CH_ERR_INVALID, wp + "NULL rollout buffer array");
+        if (rb.n_steps < 1 || rb.act_dim < h->NC * 4 || rb.act_dim > 256)
+            return fail(h, CH_ERR_INVALID, wp + "n_steps >= 1 and num_drones * 4 = " + std::to_string(h->NC * 4) +
+                                               " <= act_dim <= 256 required");
+        if (rb.n_steps != m0.rb.n_steps || rb.act_dim != m0.rb.act_dim)
+            return fail(h, CH_ERR_INVALID, wp + "n_steps and act_dim must be member 0's");
+        if (!same_mlp_arch(c.actor, m0.actor) || !same_mlp_arch(c.critic, m0.critic))
+            return fail(h, CH_ERR_INVALID, wp + "architecture (dims, activation, clip, splits) differs from member 0's");
+        for (float* a : arrays)
+            if (!writable.insert(a).second) return fail(h, CH_ERR_INVALID, wp + "a writable buffer is shared with another array or member");
+    }
+    const RoPopSlice s1 = ro_pop_slice(h->E, P, P > 1 ? 1 : 0, obs_dim, h->NC, m0.rb.act_dim);
+    if ((reinterpret_cast<uintptr_t>(sio->obs) | reinterpret_cast<uintptr_t>(sio->terminal_obs) | (uintptr_t)(s1.obs * 4)) & 15)
+        return fail(h, CH_ERR_INVALID, w + "obs buffers must be 16-byte aligned");
+    for (int p = 0; p < P; ++p)
+        if (reinterpret_cast<uintptr_t>(members[p].rb.obs) & 15)
+            return fail(h, CH_ERR_INVALID, w + "member " + std::to_string(p) + ": obs buffers must be 16-byte aligned");
+    const int32_t T = m0.rb.n_steps, act_dim = m0.rb.act_dim;
+    // the flush period of a solo handle of E envs, so that every f32 operation comes in the solo call's order
+    const int kTvEvery = ro_tv_every(E, obs_dim);
+    const long long cap = (long long)E * kTvEvery;
+    // the members' arguments: segs (actor, critic) on the member's rows of the handle's obs, the critic over its queue
+    // slice, and its RolloutArgs (the solo epilogue path's, copy_obs on every step); the queue's pointers come later
+    struct Member { MlpArgs segs[2], ftv; RolloutArgs a, ap; };
+    std::vector<Member> mb((size_t)P);
+    HIP_TRY(h, hipSetDevice(h->device));   // (the plans ask the device for its CU count)
+    MlpPlan plan[kRoPopKinds] = {};
+    for (int p = 0; p < P; ++p) {
+        const ch_rollout_member& c = members[p];
+        const std::string wp = "ch_rollout_collect_pop: member " + std::to_string(p);
+        const RoPopSlice sl = ro_pop_slice(h->E, P, p, obs_dim, h->NC, act_dim);
+        Member& m = mb[(size_t)p];
+        int rc;
+        if ((rc = policy_args(h, c.actor, sio->obs + sl.obs, io->mean + sl.mean, m.segs[0], (wp + " (actor)").c_str()))) return rc;
+        if ((rc = policy_args(h, c.critic, sio->obs + sl.obs, io->value + sl.row, m.segs[1], (wp + " (critic)").c_str()))) return rc;
+        if (c.actor->dims[c.actor->n_layers] != act_dim || c.critic->dims[c.critic->n_layers] != 1)
+            return fail(h, CH_ERR_INVALID, wp + ": actor output must be act_dim wide, critic output 1");
+        for (MlpArgs& sg : m.segs) { sg.rows = E; sg.env_n = h->envi + sl.env; }
+        std::string err;
+        float one = 0.0f;   // (the queue is allocated after the checks: a placeholder until then)
+        if ((rc = mlp_args(c.critic, &one, cap, &one, m.ftv, err))) return fail(h, rc, wp + ": " + err);
+        m.ftv.kcap = std::min(m.ftv.dims[0], h->NC * 86);
+        MlpPlan mine[kRoPopKinds];
+        const bool fits = mlp_pop_plan(m.segs, 2, mine[kRoPopStep]) && mlp_pop_plan(&m.segs[1], 1, mine[kRoPopLast]) &&
+                          (!bootstrap_truncated || mlp_pop_plan(&m.ftv, 1, mine[kRoPopFlush]));
+        if (!fits) return fail(h, CH_ERR_UNSUPPORTED, wp + ": the nets are not a k_mlp2 launch (no k_mlp / store-kernel path here)");
+        for (int k = 0; k < kRoPopKinds; ++k) {
+            if (k == kRoPopFlush && !bootstrap_truncated) continue;
+            if (p == 0) plan[k] = mine[k];
+            else if (!same_mlp_plan(plan[k], mine[k]))
+                return fail(h, CH_ERR_UNSUPPORTED, wp + ": its forward plan (packed or raw weights, alignment) differs from member 0's");
+        }
+        RolloutArgs& a = m.a;
+        std::memset(&a, 0, sizeof(a));
+        a.T = T; a.rows = E; a.obs_dim = obs_dim; a.act_dim = act_dim; a.env_act_dim = h->NC * 4;
+        a.mean_ld = act_dim; a.value_ld = 1; a.tv_ld = 1; a.post_prev = 1; a.copy_obs = 1;
+        a.obs = c.rb.obs; a.actions = c.rb.actions; a.rewards = c.rb.rewards; a.episode_starts = c.rb.episode_starts;
+        a.values = c.rb.values; a.log_probs = c.rb.log_probs; a.advantages = c.rb.advantages; a.returns = c.rb.returns;
+        a.last_episode_starts = c.rb.last_episode_starts;
+        a.reward = sio->reward + sl.row; a.terminated = sio->terminated + sl.row; a.truncated = sio->truncated + sl.row;
+        a.gamma = c.gamma;
+        a.gamma_lambda = (float)((double)c.gamma * (double)c.gae_lambda);   // SB3: float32(self.gamma * self.gae_lambda)
+        a.obs_now = sio->obs + sl.obs; a.mean = io->mean + sl.mean; a.value = io->value + sl.row;
+        a.log_std = c.log_std; a.seed = c.seed; a.env_actions = io->env_actions + sl.env_actions;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ch_rollout_state& q = h->ro;
+    if (bootstrap_truncated) {
+        int rc;
+        if ((rc = grow(h, (void**)&q.tv_obs, &q.tv_obs_bytes, sizeof(float) * (size_t)cap * P * obs_dim)) ||
+            (rc = grow(h, (void**)&q.tv_row, &q.tv_row_bytes, sizeof(long long) * (size_t)cap * P)) ||
+            (rc = grow(h, (void**)&q.tv_val, &q.tv_val_bytes, sizeof(float) * (size_t)cap * P)) ||
+            (rc = grow(h, (void**)&q.tv_count, &q.tv_count_bytes, sizeof(int) * (size_t)P)))
+            return rc;
+        HIP_TRY(h, hipMemsetAsync(q.tv_count, 0, sizeof(int) * (size_t)P, st));
+        for (int p = 0; p < P; ++p) {
+            const RoPopSlice sl = ro_pop_slice(h->E, P, p, obs_dim, h->NC, act_dim);
+            Member& m = mb[(size_t)p];
+            // V(terminal obs) over the member's queue slice: whole (12, 86) blocks, zero past the constructor's drones
+            m.ftv.x = q.tv_obs + (size_t)sl.queue * obs_dim;
+            m.ftv.y = q.tv_val + sl.queue;
+            m.ftv.rows_dev = q.tv_count + p;
+            m.ftv.vec_w &= ~(1 << 7);   // (the placeholder's alignment)
+            if (reinterpret_cast<uintptr_t>(m.ftv.x) % 16 == 0 && m.ftv.dims[0] % 4 == 0) m.ftv.vec_w |= 1 << 7;
+            RolloutArgs& a = m.a;
+            a.defer = 1; a.term_obs = sio->terminal_obs + sl.obs; a.tv_obs = q.tv_obs + (size_t)sl.queue * obs_dim;
+            a.tv_count = q.tv_count + p; a.tv_row = q.tv_row + sl.queue;
+            m.ap = a;
+            m.ap.rows = cap;
+            m.ap.terminal_value = q.tv_val + sl.queue;
+        }
+    }
+    // the staging slot: not before the copy that read it last is done (two calls ago; the device block behind it is
+    // read by that call's launches, which this call's copy follows in the stream)
+    ch_rollout_pop::Slot& slot = pop->slot[pop->calls++ % kRoPopSlots];
+    if (slot.queued) {
+        HIP_TRY(h, hipEventSynchronize(slot.copied));
+        slot.queued = false;
+    }
+    const int roles[2] = {kRoleSample, kRoleValue}, tv_role = kRoleTvApply;
+    for (int p = 0; p < P; ++p) {
+        Member& m = mb[(size_t)p];
+        PopMlp* host[kRoPopKinds];
+        for (int k = 0; k < kRoPopKinds; ++k) host[k] = reinterpret_cast<PopMlp*>(slot.host + pop->off[k]) + p;
+        mlp_pop_fill(*host[kRoPopStep], plan[kRoPopStep], m.segs, roles, &m.a);
+        if (bootstrap_truncated) mlp_pop_fill(*host[kRoPopFlush], plan[kRoPopFlush], &m.ftv, &tv_role, &m.ap);
+        else std::memset(host[kRoPopFlush], 0, sizeof(PopMlp));
+        mlp_pop_fill(*host[kRoPopLast], plan[kRoPopLast], &m.segs[1], nullptr, nullptr);
+    }
+    HIP_TRY(h, hipMemcpyAsync(slot.dev, slot.host, pop->bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipEventRecord(slot.copied, st));
+    slot.queued = true;
+    const PopMlp* dev[kRoPopKinds];
+    for (int k = 0; k < kRoPopKinds; ++k) dev[k] = reinterpret_cast<const PopMlp*>(slot.dev + pop->off[k]);
+    auto flush = [&]() -> hipError_t {
+        hipError_t e = launch_mlp_pop(plan[kRoPopFlush], dev[kRoPopFlush], P, 0, st);
+        if (e == hipSuccess) e = hipMemsetAsync(q.tv_count, 0, sizeof(int) * (size_t)P, st);
+        return e;
+    };
+    // per step: every member's actor and critic on its rows of the handle's obs with the store in their epilogues
+    // (step t - 1's post and the copy of obs[t] into the member's buffer in the critic's), the flush where a solo
+    // handle of E envs has it, one env step of the whole handle into its own obs buffer
+    ch_step_io s = collect_step_io(sio, io->env_actions);
+    for (int32_t t = 0; t < T; ++t) {
+        HIP_TRY(h, launch_mlp_pop(plan[kRoPopStep], dev[kRoPopStep], P, t, st));
+        if (bootstrap_truncated && t > 0 && t % kTvEvery == 0) HIP_TRY(h, flush());
+        if (int rc = ch_step(h, &s, stream)) return rc;
+    }
+    // the tail, as the solo epilogue path: the last step's post, the last flush, V(obs after the last step), GAE
+    HIP_TRY(h, launch_rollout_pop(dev[kRoPopStep], P, E, 0, T, st));
+    if (bootstrap_truncated) HIP_TRY(h, flush());
+    HIP_TRY(h, launch_mlp_pop(plan[kRoPopLast], dev[kRoPopLast], P, 0, st));
+    HIP_TRY(h, launch_rollout_pop(dev[kRoPopStep], P, E, 2, T, st));
+    return CH_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ch_marl_rollout_collect and ch_marl_rollout_collect_log (`ring`: NULL, or the episode ring every step is recorded in)
 static int marl_rollout_collect(ch_handle* h, const ch_marl_rollout* rb, const ch_marl_rollout_io* io, const ch_mlp* policy,

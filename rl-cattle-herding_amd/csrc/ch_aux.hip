@@ -57,6 +57,26 @@ namespace {
 constexpr int kRollThreads = 256;
 }  // namespace
 
+// the store's first half, one wave per env: the post of step t - 1 in lane 0 (post: else the env's last episode start is
+// read), and, where that queues a deferred bootstrap, the wave's copy of the terminal observation into the queue;
+// lane 0 returns the episode start of step t.  post() and t() are read where the solo kernel always read them.
+template <class FP, class FT>
+__device__ __forceinline__ float rollout_wave_post(const RolloutArgs& a, FT t, long long e, int lane, FP post) {
+    float les = 0.0f;
+    bool queue = false;
+    if (lane == 0) les = post() ? rollout_post_env(a, t() - 1, e, &queue) : a.last_episode_starts[e];
+    if (__ballot(queue)) {
+        // deferred bootstrap: the terminal observation of step t - 1 into the queue (the wave copies it)
+        int slot = 0;
+        if (lane == 0) { slot = atomicAdd(a.tv_count, 1); a.tv_row[slot] = (long long)(t() - 1) * a.rows + e; }
+        slot = __shfl(slot, 0);
+        const float4* src = reinterpret_cast<const float4*>(a.term_obs + e * a.obs_dim);
+        float4* dst = reinterpret_cast<float4*>(a.tv_obs + (long long)slot * a.obs_dim);
+        for (int k = lane; k < a.obs_dim / 4; k += 64) dst[k] = src[k];
+    }
+    return les;
+}
+
 // one wave per env (kRollThreads / 64 envs per workgroup): the observation row into the buffer (copy_obs), the
 // Gaussian sample of every action (lane k: action k, k + 64, ...), the summed log-probability (a wave tree
 // sum), the clipped env action, value and episode start; with post_prev, the previous step's post first (one
@@ -66,18 +86,7 @@ __global__ __launch_bounds__(kRollThreads) void k_rollout_store(RolloutArgs a) {
     const long long e = (long long)blockIdx.x * (kRollThreads / 64) + (threadIdx.x >> 6);
     if (e >= a.rows) return;
     const long long row = (long long)a.t * a.rows + e;
-    float les = 0.0f;
-    bool queue = false;
-    if (lane == 0) les = a.post_prev && a.t > 0 ? rollout_post_env(a, a.t - 1, e, &queue) : a.last_episode_starts[e];
-    if (__ballot(queue)) {
-        // deferred bootstrap: the terminal observation of step t - 1 into the queue (the wave copies it)
-        int slot = 0;
-        if (lane == 0) { slot = atomicAdd(a.tv_count, 1); a.tv_row[slot] = (long long)(a.t - 1) * a.rows + e; }
-        slot = __shfl(slot, 0);
-        const float4* src = reinterpret_cast<const float4*>(a.term_obs + e * a.obs_dim);
-        float4* dst = reinterpret_cast<float4*>(a.tv_obs + (long long)slot * a.obs_dim);
-        for (int k = lane; k < a.obs_dim / 4; k += 64) dst[k] = src[k];
-    }
+    const float les = rollout_wave_post(a, [&] { return a.t; }, e, lane, [&] { return a.post_prev && a.t > 0; });
     if (a.post_only) return;
     if (a.copy_obs) {
         const float4* src = reinterpret_cast<const float4*>(a.obs_now + e * a.obs_dim);
@@ -120,10 +129,10 @@ __global__ void k_rollout_apply(RolloutArgs a, const float* tv_val) {
 // recursion is serial in the step; its inputs are not: each chunk of kGaeChunk steps is loaded at once (one memory
 // round trip per chunk instead of per step), then folded backwards.
 constexpr int kGaeChunk = 16;
-__global__ void k_rollout_gae(RolloutArgs a) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.rows) return;
-    const float les = a.post_prev ? rollout_post_env(a, a.T - 1, e) : a.last_episode_starts[e];   // the last step's post
+// env e's pass; POST: first the last step's post where a.post_prev says so (the solo kernel), else never
+template <bool POST>
+__device__ __forceinline__ void rollout_gae_env(const RolloutArgs& a, long long e) {
+    const float les = POST && a.post_prev ? rollout_post_env(a, a.T - 1, e) : a.last_episode_starts[e];   // the last step's post
     const float g = a.gamma, gl = a.gamma_lambda;
     float last = 0.0f;
     float nnt = 1.0f - les, nv = a.value[e * a.value_ld];   // the step after s: (1 - its episode start), its value
@@ -146,6 +155,40 @@ __global__ void k_rollout_gae(RolloutArgs a) {
             nnt = 1.0f - es[i]; nv = vl[i];
         }
     }
+}
+
+__global__ void k_rollout_gae(RolloutArgs a) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.rows) return;
+    rollout_gae_env<true>(a, e);
+}
+
+// ch_rollout_collect_pop's post-only store and GAE: the member is blockIdx.y, its RolloutArgs the `ro`
+// of its entry of the device table the forwards read (pointers offset to the member's slice, rows = its envs), the step
+// a kernel argument.  WHICH 0: k_rollout_store's post_only form for step t - 1 (one wave per env); 2: k_rollout_gae
+// after it (one env per thread, no post).  The per-row bodies are the solo kernels'.
+template <int WHICH>
+__global__ __launch_bounds__(WHICH == 0 ? kRollThreads : 64) void k_rollout_pop(const PopMlp* __restrict__ tab, int t) {
+    const RolloutArgs& a = tab[blockIdx.y].ro;
+    if constexpr (WHICH == 0) {
+        const long long e = (long long)blockIdx.x * (kRollThreads / 64) + (threadIdx.x >> 6);
+        if (e >= a.rows) return;
+        (void)rollout_wave_post(a, [&] { return t; }, e, threadIdx.x & 63, [] { return true; });
+    } else {
+        const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (e >= a.rows) return;
+        rollout_gae_env<false>(a, e);
+    }
+}
+
+hipError_t launch_rollout_pop(const PopMlp* tab, int members, long long rows, int which, int tstep, hipStream_t st) {
+    if (members < 1 || members > 65535 || rows < 1 || (which != 0 && which != 2)) return hipErrorInvalidValue;
+    if (which == 0)
+        hipLaunchKernelGGL(k_rollout_pop<0>, dim3((unsigned)((rows + kRollThreads / 64 - 1) / (kRollThreads / 64)), (unsigned)members),
+                           dim3(kRollThreads), 0, st, tab, tstep);
+    else
+        hipLaunchKernelGGL(k_rollout_pop<2>, dim3((unsigned)((rows + 63) / 64), (unsigned)members), dim3(64), 0, st, tab, tstep);
+    return hipGetLastError();
 }
 
 // ---- the DTDE (RLlib) per-agent rollout (ch_marl_rollout_collect; DTDECattleHerder.py:62-97, marl_wrapper.py:77-119)

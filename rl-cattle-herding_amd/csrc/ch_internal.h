@@ -371,6 +371,26 @@ hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const
                             const RolloutArgs* ro = nullptr);
 // launch_mlp_multi's plan for these segments is one k_mlp2 launch (mlp_plan(...).v2: the rollout epilogues need it)
 bool mlp_multi_fits(const MlpArgs* segs, int nseg);
+// The population collection (ch_rollout_collect_pop): one entry per member of a device table that
+// k_mlp2_pop (ch_policy.hip) and k_rollout_pop (ch_aux.hip) index by blockIdx.y.  Up to two segments of one member
+// (its actor and critic, or its critic alone), each pointer offset to the member's slice, rows = the member's envs;
+// ro.t is not read: the step is a kernel argument.
+struct PopMlp {
+    MlpArgs seg[2];
+    int nseg;
+    int start[3];              // first workgroup (blockIdx.x) of each segment (start[nseg] = grid.x)
+    int role[2];
+    RolloutArgs ro;
+};
+// mlp_plan for one member's segments on the current device (the row, rt, lda, ldh and LDS bytes that member's solo
+// launch gets); false when the plan is not one k_mlp2 launch
+bool mlp_pop_plan(const MlpArgs* segs, int nseg, MlpPlan& p);
+void mlp_pop_fill(PopMlp& m, const MlpPlan& p, const MlpArgs* segs, const int* roles, const RolloutArgs* ro);
+// grid (p.start[p.n], members): the plan's k_mlp2 row as k_mlp2_pop over a device table of `members` entries
+hipError_t launch_mlp_pop(const MlpPlan& p, const PopMlp* tab, int members, int tstep, hipStream_t st);
+// k_rollout_pop over the same kind of table (entry.ro): which = 0 the post of step tstep - 1 alone (launch_rollout's
+// post_only store), 2 GAE (without the last post: the epilogue path has run it)
+hipError_t launch_rollout_pop(const PopMlp* tab, int members, long long rows, int which, int tstep, hipStream_t st);
 // diagnostics (ch__mlp_last_launch): which forward kernel (ch_mlp_plan.h MlpKernel) launch_mlp_multi launched last
 extern MlpLaunch g_mlp_last_launch;
 extern long long g_mlp_launches[kMlpKernels];   // launches of each kernel since the library was loaded

@@ -317,9 +317,20 @@ __device__ __forceinline__ void mlp2_lds_barrier() {
 // counts.
 // RT row tiles of 16 per workgroup (RT > 1: the hidden buffer of odd layers reuses the input rows' region, which is
 // dead after layer 0 -- see mlp2_lds_floats).
-template <int NW, int TW, int RT>
+// tstep(): the collection step the rollout roles store.  The solo kernels read it from `ro` where it is used (StepOfRo:
+// the code they always had); the population kernel, whose `ro` is a table entry uploaded once per call, has it as a
+// kernel argument (StepArg).
+struct StepOfRo {
+    const RolloutArgs& ro;
+    __device__ __forceinline__ int operator()() const { return ro.t; }
+};
+struct StepArg {
+    int t;
+    __device__ __forceinline__ int operator()() const { return t; }
+};
+template <int NW, int TW, int RT, class TS>
 __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int lda, int ldh, int role,
-                                          const RolloutArgs& ro) {
+                                          const RolloutArgs& ro, const TS tstep) {
     extern __shared__ __align__(16) float sm[];
     constexpr int TMR = kTM * RT;      // rows of the workgroup
     static_assert(TMR <= 64, "the live-width scan reduces the rows in wave 0");
@@ -568,13 +579,13 @@ __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int l
         mlp2_lds_barrier();
         for (int idx = tid; idx < nrow * NA; idx += kT) {
             const int r = idx / NA, k = idx - r * NA;
-            lp[r * ldh + k] = rollout_sample(ro, ro.t, k, row0 + r, lp[r * ldh + k]);
+            lp[r * ldh + k] = rollout_sample(ro, tstep(), k, row0 + r, lp[r * ldh + k]);
         }
         mlp2_lds_barrier();
         if (tid < nrow) {
             float s = 0.0f;
             for (int k = 0; k < NA; ++k) s += lp[tid * ldh + k];
-            ro.log_probs[(long long)ro.t * ro.rows + row0 + tid] = s;
+            ro.log_probs[(long long)tstep() * ro.rows + row0 + tid] = s;
         }
     } else if (role == kRoleValue) {
         // the critic's values (staged like the actor's means), the previous step's post (reward, next episode
@@ -586,13 +597,13 @@ __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int l
             const long long e = row0 + tid;
             int slot = -1;
             if (e < a.rows) {
-                ro.values[(long long)ro.t * ro.rows + e] = vl[tid * ldh];
+                ro.values[(long long)tstep() * ro.rows + e] = vl[tid * ldh];
                 bool q = false;
-                const float les = ro.t > 0 ? rollout_post_env(ro, ro.t - 1, e, &q) : ro.last_episode_starts[e];
-                ro.episode_starts[(long long)ro.t * ro.rows + e] = les;
+                const float les = tstep() > 0 ? rollout_post_env(ro, tstep() - 1, e, &q) : ro.last_episode_starts[e];
+                ro.episode_starts[(long long)tstep() * ro.rows + e] = les;
                 if (q) {
                     slot = atomicAdd(ro.tv_count, 1);
-                    ro.tv_row[slot] = (long long)(ro.t - 1) * ro.rows + e;
+                    ro.tv_row[slot] = (long long)(tstep() - 1) * ro.rows + e;
                 }
             }
             qslot[tid] = slot;
@@ -610,7 +621,7 @@ __device__ __forceinline__ void mlp2_body(const MlpArgs& a, long long blk, int l
             const int nr = (int)min((long long)TMR, a.rows - row0);
             for (int k = tid; k < nr * nq4; k += kT) {
                 const int r = k / nq4, c = k - r * nq4;
-                reinterpret_cast<float4*>(ro.obs + ((long long)ro.t * ro.rows + row0 + r) * ro.obs_dim)[c] =
+                reinterpret_cast<float4*>(ro.obs + ((long long)tstep() * ro.rows + row0 + r) * ro.obs_dim)[c] =
                     reinterpret_cast<const float4*>(a.x + (row0 + r) * (long long)ro.obs_dim)[c];
             }
         }

@@ -262,7 +262,22 @@ __global__ __launch_bounds__(64 * NW, SHARE ? 4 : ((NW == 4 && RT == 2) ? 2 : 1)
     int sg = 0;
     if (m.nseg > 1 && (int)blockIdx.x >= m.start[1]) sg = 1;
     if (m.nseg > 2 && (int)blockIdx.x >= m.start[2]) sg = 2;
-    mlp2_body<NW, TW, RT>(m.seg[sg], (long long)blockIdx.x - m.start[sg], m.lda, m.ldh, m.role[sg], m.ro);
+    mlp2_body<NW, TW, RT>(m.seg[sg], (long long)blockIdx.x - m.start[sg], m.lda, m.ldh, m.role[sg], m.ro, StepOfRo{m.ro});
+}
+
+// ch_rollout_collect_pop's forwards: P members of one architecture in one launch.  blockIdx.y is the
+// member and selects its entry of a device table built once per call; blockIdx.x selects segment and tile as in
+// k_mlp2.  The entry goes to mlp2_body by reference: the table is read-only and `__restrict__` and the member is
+// wave-uniform, so its fields come by scalar loads and the run-time-indexed arrays stay in memory as they stay in
+// k_mlp2's kernel-argument segment.  Every pointer of an entry is offset on the host to the member's slice and
+// rows = the member's env count, so each row index in the body is member-local and its `< rows` guards keep a
+// member's tail tile off the next member's rows.  Only the step changes between launches: it is a kernel argument.
+template <int NW, int TW, bool SHARE = false, int RT = 1>
+__global__ __launch_bounds__(64 * NW, SHARE ? 4 : ((NW == 4 && RT == 2) ? 2 : 1)) void k_mlp2_pop(
+    const PopMlp* __restrict__ tab, int lda, int ldh, int tstep) {
+    const PopMlp& m = tab[blockIdx.y];
+    const int sg = m.nseg > 1 && (int)blockIdx.x >= m.start[1] ? 1 : 0;
+    mlp2_body<NW, TW, RT>(m.seg[sg], (long long)blockIdx.x - m.start[sg], lda, ldh, m.role[sg], m.ro, StepArg{tstep});
 }
 
 // ch_mlp_pack: layer li's weights into the [tile][pair][half][lane][4] layout (zero past N and K)
@@ -316,6 +331,17 @@ static const void* mlp_fn(int kernel) {
 #undef CH_FN
 }
 
+static const void* mlp_pop_fn(int kernel) {
+#define CH_FN(K, ...) case K: return reinterpret_cast<const void*>(&__VA_ARGS__)
+    switch (kernel) {
+        CH_FN(kMlp2_4_2, k_mlp2_pop<4, 2>); CH_FN(kMlp2_8_2, k_mlp2_pop<8, 2>); CH_FN(kMlp2_8_1, k_mlp2_pop<8, 1>);
+        CH_FN(kMlp2_8_1s, k_mlp2_pop<8, 1, true>); CH_FN(kMlp2_4_4_r2, k_mlp2_pop<4, 4, false, 2>);
+        CH_FN(kMlp2_4_4_r4, k_mlp2_pop<4, 4, false, 4>); CH_FN(kMlp2_8_1_r2, k_mlp2_pop<8, 1, false, 2>);
+        default: return nullptr;
+    }
+#undef CH_FN
+}
+
 // once per device (the attribute is per device context): every kernel's dynamic-LDS opt-in and the CU count
 static hipError_t mlp_device(int& cus) {
     static std::atomic<int> cus_of[64];   // 0: not set up yet
@@ -327,6 +353,9 @@ static hipError_t mlp_device(int& cus) {
     for (int k = 1; k < kMlpKernels; ++k) {
         e = hipFuncSetAttribute(mlp_fn(k), hipFuncAttributeMaxDynamicSharedMemorySize, kMlpTable[k].lds_attr());
         if (e != hipSuccess) return e;
+        if (mlp_pop_fn(k) && (e = hipFuncSetAttribute(mlp_pop_fn(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      kMlpTable[k].lds_attr())) != hipSuccess)
+            return e;
     }
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
     slot.store(cus, std::memory_order_relaxed);
@@ -385,5 +414,33 @@ hipError_t launch_mlp_multi(const MlpArgs* segs, int nseg, hipStream_t st, const
 }
 
 hipError_t launch_mlp(const MlpArgs& a, hipStream_t st) { return launch_mlp_multi(&a, 1, st); }
+
+bool mlp_pop_plan(const MlpArgs* segs, int nseg, MlpPlan& p) {
+    int cus = 0;
+    if (nseg < 1 || nseg > 2 || mlp_device(cus) != hipSuccess) return false;
+    p = mlp_plan(segs, nseg, cus, mlp_switches());
+    return p.v2 && p.n == nseg && mlp_pop_fn(p.kernel[0]) != nullptr;
+}
+
+void mlp_pop_fill(PopMlp& m, const MlpPlan& p, const MlpArgs* segs, const int* roles, const RolloutArgs* ro) {
+    std::memset(&m, 0, sizeof(m));
+    for (int i = 0; i < p.n; ++i) {
+        m.seg[i] = segs[i];
+        m.role[i] = roles ? roles[i] : kRoleNone;
+    }
+    std::copy(p.start, p.start + 3, m.start);
+    m.nseg = p.n;
+    if (ro) m.ro = *ro;
+}
+
+hipError_t launch_mlp_pop(const MlpPlan& p, const PopMlp* tab, int members, int tstep, hipStream_t st) {
+    const void* fn = mlp_pop_fn(p.kernel[0]);
+    if (!p.v2 || !fn || members < 1 || members > 65535) return hipErrorInvalidValue;
+    int lda = p.lda, ldh = p.ldh;
+    void* args[] = {&tab, &lda, &ldh, &tstep};
+    (void)hipLaunchKernel(fn, dim3((unsigned)p.start[p.n], (unsigned)members), dim3(64u * kMlpTable[p.kernel[0]].nw), args,
+                          (size_t)p.lds, st);
+    return hipGetLastError();
+}
 
 }  // namespace ch

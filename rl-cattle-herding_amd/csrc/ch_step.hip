@@ -43,7 +43,7 @@ void k_step2_actor(StepParams<R> p, FusedActor f) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     __builtin_amdgcn_s_setprio(0);   // (the drone wave's raised priority)
     if (ts) ts[14] = (long long)wall_clock64();
-    mlp2_body<CH_V2_MAX_BLOCK / 64, 1, 1>(f.a, (long long)blockIdx.x, f.lda, f.ldh, kRoleSample, f.ro);
+    mlp2_body<CH_V2_MAX_BLOCK / 64, 1, 1>(f.a, (long long)blockIdx.x, f.lda, f.ldh, kRoleSample, f.ro, StepOfRo{f.ro});
     if (ts) ts[15] = (long long)wall_clock64();
 }
 
