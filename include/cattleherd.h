@@ -447,6 +447,56 @@ int ch_rollout_collect_log(ch_handle* h, const ch_rollout* rb, const ch_rollout_
                            const ch_mlp* critic, const float* log_std, uint64_t seed, float gamma, float gae_lambda,
                            int32_t bootstrap_truncated, const ch_ep_ring* ring, void* stream);
 
+/* ---- A population's training log: per-member episode rings and a fitness table on the device -----------------------
+ * Replaces: P ep_info_buffer deques, one per member of a population that collects with ch_rollout_collect_pop; the
+ * reference has no counterpart for running the members together.  Member p of n_members owns envs [pE, (p + 1)E) of the
+ * handle, E = n_envs / n_members, and row p of every array.  CTDE handles only (CH_ERR_UNSUPPORTED for a MARL handle).
+ * All arrays are caller-owned device memory; one window for every member. */
+typedef struct ch_ep_ring_pop {
+    int32_t  window;      /* W >= 1, the same for every member */
+    int32_t  n_members;   /* P >= 1; the handle's n_envs must be a multiple of it, E = n_envs / P */
+    double*  ep_return;   /* device [P][W] */
+    int32_t* ep_length;   /* device [P][W] */
+    int32_t* ep_env;      /* device [P][W]: the MEMBER-LOCAL env index, e - pE */
+    int64_t* total;       /* device [P]: member p's episodes appended since begin; its episode k lives in slot k % W */
+} ch_ep_ring_pop;
+
+/* total[p] = 0 for every member (the slots are not cleared). */
+int ch_ep_ring_pop_begin(ch_handle* h, const ch_ep_ring_pop* ring, void* stream);
+
+/* After a ch_step with CH_STEP_AUTORESET on the same stream.  CONTRACT: row p of the four arrays is afterwards bit for
+ * bit what ch_ep_ring_record writes to a solo ring of window W on a handle of E envs whose reset_happened and
+ * episode_stats are rows [pE, (p + 1)E) of this io's: member p's C_p ended envs in ascending env order, rank r to slot
+ * (total[p] + r) % W, only ranks r >= C_p - W written, then total[p] += C_p; a member with C_p == 0 writes nothing, not
+ * even total[p].  One launch whatever P is: workgroup p is the solo recorder on the member's slice (the same counting
+ * and ranking passes in chunks of 1024 envs; plain stores, no atomics, nothing shared between workgroups).
+ * CH_ERR_INVALID (ch_last_error says which): a NULL ring, io or handle, window < 1, n_members < 1, a missing ring array,
+ * n_envs % n_members != 0, an io without reset_happened or episode_stats. */
+int ch_ep_ring_pop_record(ch_handle* h, const ch_ep_ring_pop* ring, const ch_step_io* io, void* stream);
+
+/* ch_rollout_collect_pop with the members' episode rings: with ring != NULL, ch_ep_ring_pop_record's launch runs once
+ * per step, right after the step's ch_step and before anything that can overwrite reset_happened or episode_stats
+ * (where ch_rollout_collect_log records); io->step->episode_stats is then required and ring->n_members must equal
+ * n_members (CH_ERR_INVALID; checked with everything else before the first launch).  ring == NULL is
+ * ch_rollout_collect_pop exactly.  The members' buffers and the env state do not depend on the ring.  The call does not
+ * begin the ring: one ring spans the collections of a training run. */
+int ch_rollout_collect_pop_log(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
+                               const ch_rollout_io* io, int32_t bootstrap_truncated, const ch_ep_ring_pop* ring,
+                               void* stream);
+
+/* The fitness table a population is compared on: out_dev[p] = {count = min(total[p], W), mean return, mean length,
+ * total[p] as a double}, CH_EP_RING_POP_SUMMARY doubles per member.  Handle-free (errors through ch_last_error(NULL));
+ * one launch, grid (P), stream-ordered, no host synchronisation.  The means are float64 over the ring's content in
+ * chronological order, oldest first -- position i = 0 .. count - 1 is episode total - count + i, slot
+ * (total - count + i) % W -- in this FIXED ORDER: one 64-thread workgroup per member; thread t starts from 0.0 and adds
+ * positions t, t + 64, t + 128, ... in that order; the 64 thread sums are added by a halving tree (for w = 32, 16, ..,
+ * 1: s[t] += s[t + w] for t < w); the mean is s[0] / count.  count == 0 gives NaN means.
+ * DIFFERENCE: the returns are not rounded to 6 decimals here; Monitor's rounding stays on the host path (train_log.py
+ * summary_of), so a mean return can differ from rollout/ep_rew_mean in the 7th decimal.
+ * CH_ERR_INVALID: a NULL ring or out_dev, window < 1, n_members < 1, a missing ring array. */
+#define CH_EP_RING_POP_SUMMARY 4
+int ch_ep_ring_pop_summary(const ch_ep_ring_pop* ring, double* out_dev, void* stream);
+
 /* ---- Device-side VecNormalize: running observation / return statistics for the CTDE PPO path -----------------
  * Replaces: stable_baselines3 VecNormalize(venv, training, norm_obs, norm_reward, clip_obs, clip_reward, gamma,
  * epsilon) around the reference's VecEnv, and its two RunningMeanStd (obs_rms over the observation features, ret_rms
@@ -935,6 +985,17 @@ int ch_ppo_train_pop(ch_ppo_pop* pop, const ch_ppo_member* members, int32_t n_me
 int64_t ch_explained_variance_scratch(int64_t n);
 int ch_explained_variance(const float* values, const float* returns, int64_t n, double* out_dev, double* scratch,
                           void* stream);
+
+/* Replaces: n_members calls of ch_explained_variance, one per member of a population, by one set of three launches
+ * with the member as a grid dimension.  values_dev, returns_dev: DEVICE arrays of n_members device pointers, each to
+ * [n] floats (the members' buffers are separate allocations); out_dev: device double [n_members][2]; scratch: device,
+ * ch_explained_variance_pop_scratch(n, n_members) doubles ([n_members][4G]; host only, -1 for n < 1 or n_members < 1).
+ * CONTRACT: out_dev[p] is bit for bit what ch_explained_variance(values[p], returns[p], n, ...) gives: the same grid
+ * for n, the same elements per workgroup, the same per-thread and tree order (the kernels share their bodies).
+ * Handle-free; CH_ERR_INVALID for a NULL argument, n_members outside 1..65535 or n < 1. */
+int64_t ch_explained_variance_pop_scratch(int64_t n, int32_t n_members);
+int ch_explained_variance_pop(const float* const* values_dev, const float* const* returns_dev, int32_t n_members,
+                              int64_t n, double* out_dev, double* scratch, void* stream);
 
 /* ---- Native PPO minibatch update for the DTDE (RLlib) driver's shared policy ---------------------------------
  * Replaces: the minibatch step of RLlib 2.x's new-API-stack PPO learner (PPOTorchLearner.compute_loss_for_module,

@@ -35,7 +35,9 @@ EXPORTS = ("ch_default_config", "ch_create", "ch_destroy", "ch_last_error", "ch_
            "ch_marl_rollout_collect_log", "ch_marl_ppo_train_log", "ch_ppo_train_opt", "ch_norm_scratch_size",
            "ch_norm_begin", "ch_norm_obs_update", "ch_norm_obs_apply", "ch_norm_reward", "ch_rollout_collect_norm",
            "ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop", "ch_rollout_pop_create",
-           "ch_rollout_pop_destroy", "ch_rollout_collect_pop")
+           "ch_rollout_pop_destroy", "ch_rollout_collect_pop", "ch_ep_ring_pop_begin", "ch_ep_ring_pop_record",
+           "ch_rollout_collect_pop_log", "ch_ep_ring_pop_summary", "ch_explained_variance_pop_scratch",
+           "ch_explained_variance_pop")
 # the on-device evaluations' symbols: an older library (an A/B baseline loaded through CH_LIB_PATH) lacks them
 _EVAL_EXPORTS = ("ch_eval_begin", "ch_eval_record", "ch_evaluate_policy", "ch_marl_eval_begin", "ch_marl_eval_mark",
                  "ch_marl_eval_record", "ch_marl_evaluate_policy", "ch_eval_log_begin", "ch_eval_log_mark",
@@ -59,6 +61,10 @@ _NORM_EXPORTS = ("ch_norm_scratch_size", "ch_norm_begin", "ch_norm_obs_update", 
 _PPO_POP_EXPORTS = ("ch_ppo_pop_create", "ch_ppo_pop_destroy", "ch_ppo_train_pop")
 # the population collection's (cattleherd/rollout_pop.py): likewise
 _ROLLOUT_POP_EXPORTS = ("ch_rollout_pop_create", "ch_rollout_pop_destroy", "ch_rollout_collect_pop")
+# the population's training log (cattleherd/train_log.py PopulationEpisodeRing, explained_variance_pop): likewise
+_TRAIN_LOG_POP_EXPORTS = ("ch_ep_ring_pop_begin", "ch_ep_ring_pop_record", "ch_rollout_collect_pop_log",
+                          "ch_ep_ring_pop_summary", "ch_explained_variance_pop_scratch", "ch_explained_variance_pop")
+CH_EP_RING_POP_SUMMARY = 4   # ch_ep_ring_pop_summary's columns: count, mean return, mean length, total
 CH_ACT_NONE, CH_ACT_TANH, CH_ACT_RELU = 0, 1, 2
 
 
@@ -184,6 +190,12 @@ class ChEpRing(ctypes.Structure):
         [(k, ctypes.c_void_p) for k in ("ep_return", "ep_length", "ep_env", "total")]
 
 
+# a population's episode rings (ch_ep_ring_pop_*; cattleherd/train_log.py)
+class ChEpRingPop(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_int32), ("n_members", ctypes.c_int32)] + \
+        [(k, ctypes.c_void_p) for k in ("ep_return", "ep_length", "ep_env", "total")]
+
+
 # the RLlib training log's episode ring (ch_marl_ep_ring_*; cattleherd/train_log.py)
 MARL_RING_ARRAYS = ("ep_return", "agent_return", "ep_length", "agent_length", "ep_env", "total", "acc_return",
                     "acc_length", "acc_steps", "env_steps", "agent_steps")
@@ -299,6 +311,12 @@ def lib():
         L.ch_ppo_train_log.argtypes = L.ch_ppo_train.argtypes
         L.ch_explained_variance_scratch.argtypes = [i64]
         L.ch_explained_variance.argtypes = [vp, vp, i64, vp, vp, vp]
+    if hasattr(L, "ch_ep_ring_pop_record"):
+        L.ch_ep_ring_pop_begin.argtypes = [vp, P(ChEpRingPop), vp]
+        L.ch_ep_ring_pop_record.argtypes = [vp, P(ChEpRingPop), P(ChStepIO), vp]
+        L.ch_ep_ring_pop_summary.argtypes = [P(ChEpRingPop), vp, vp]
+        L.ch_explained_variance_pop_scratch.argtypes = [i64, i32]
+        L.ch_explained_variance_pop.argtypes = [vp, vp, i32, i64, vp, vp, vp]
     if hasattr(L, "ch_marl_ep_ring_record"):
         L.ch_marl_ep_ring_begin.argtypes = [vp, P(ChMarlEpRing), vp]
         L.ch_marl_ep_ring_record.argtypes = [vp, P(ChMarlEpRing), vp, P(ChStepIO), vp]
@@ -322,7 +340,7 @@ def lib():
         L.ch_norm_obs_apply.argtypes = [N, vp, i64, vp, vp, vp]
         L.ch_norm_reward.argtypes = [N, vp, vp, vp, i64, vp, vp]
     optional = ("ch_step_n",) + _EVAL_EXPORTS + _TRAIN_LOG_EXPORTS + _MARL_TRAIN_LOG_EXPORTS + _PPO_OPT_EXPORTS + \
-        _NORM_EXPORTS + _PPO_POP_EXPORTS + _ROLLOUT_POP_EXPORTS
+        _NORM_EXPORTS + _PPO_POP_EXPORTS + _ROLLOUT_POP_EXPORTS + _TRAIN_LOG_POP_EXPORTS
     for name in EXPORTS:
         if name not in ("ch_last_error",) and (name not in optional or hasattr(L, name)):
             getattr(L, name).restype = ctypes.c_int
@@ -333,6 +351,8 @@ def lib():
         L.ch_explained_variance_scratch.restype = ctypes.c_int64
     if hasattr(L, "ch_norm_scratch_size"):
         L.ch_norm_scratch_size.restype = ctypes.c_int64
+    if hasattr(L, "ch_explained_variance_pop_scratch"):
+        L.ch_explained_variance_pop_scratch.restype = ctypes.c_int64
     _lib = L
     return L
 

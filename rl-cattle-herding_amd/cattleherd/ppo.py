@@ -387,12 +387,14 @@ class PPOUpdate:
             stats = torch.zeros((self.n_epochs * nb, _lib.CH_PPO_LOG_STATS), dtype=torch.float32, device=dev)
         return stats, opts
 
-    def _native_finish(self, stats, rb, nb, steps):
+    def _native_finish(self, stats, rb, nb, steps, fill_log=True):
         """The bookkeeping behind the launches of ``steps`` minibatch steps: the log, or what ``n_updates`` and
-        ``last_stats`` will be read from.  Returns ``steps``."""
+        ``last_stats`` will be read from.  ``fill_log=False``: the caller gathers and records a logging update's
+        record itself (a population reads all its members' at once).  Returns ``steps``."""
         self.sgd_steps += steps
         if self.log_stats:
-            self._fill_log(stats, rb, nb)
+            if fill_log:
+                self._fill_log(stats, rb, nb)
         elif self._opts:
             # n_updates and last_stats are read when asked for: the epochs that ran a minibatch are counted on the
             # device (stream-ordered, no synchronisation) and only the latest table is kept
@@ -405,17 +407,29 @@ class PPOUpdate:
 
     def _fill_log(self, stats, rb, nb):
         """SB3 ``PPO.train``'s logger record from the call's statistics, the buffer's explained variance and the
-        current ``log_std``: everything is gathered on the device and read once."""
-        import numpy as np
-        from .train_log import explained_variance, sb3_train_record
-        torch = _torch()
+        current ``log_std``: everything is gathered on the device (``_log_gather``) and read once, then recorded
+        (``_log_record``)."""
+        from .train_log import explained_variance
         ev = explained_variance(rb.values.view(-1), rb.returns.view(-1))
+        self._log_record(self._log_gather(stats, ev).cpu().numpy(), stats.shape, nb)      # the one read
+
+    def _log_gather(self, stats, ev):
+        """What the record is made of, as one float64 device tensor: the statistics table flattened, ``ev`` (the two
+        outputs of the explained variance), the mean standard deviation."""
+        torch = _torch()
         std = torch.exp(self.model.log_std.data).mean().double().view(1)
-        host = torch.cat([stats.double().view(-1), ev, std]).cpu().numpy()      # the one read
-        st = host[:stats.numel()].reshape(stats.shape)
+        return torch.cat([stats.double().view(-1), ev.view(-1), std])
+
+    def _log_record(self, host, shape, nb):
+        """``last_log``, ``last_stats`` and ``n_updates`` from ``_log_gather``'s tensor on the host (numpy float64; the
+        table's ``shape``)."""
+        import numpy as np
+        from .train_log import sb3_train_record
+        size = int(np.prod(shape))
+        st = host[:size].reshape(shape)
         self._last_stats = st.astype(np.float32)   # (exact: the values were float32)
         self.last_log, epochs = sb3_train_record(
-            st, nb, self.ent_coef, self.vf_coef, self.clip_range, host[stats.numel()], host[-1], self._n_updates,
+            st, nb, self.ent_coef, self.vf_coef, self.clip_range, host[size], host[-1], self._n_updates,
             learning_rate=self.learning_rate if self._log_lr else None, clip_range_vf=self.clip_range_vf)
         self._n_updates += epochs
 

@@ -4,7 +4,9 @@ in one set of launches (``ch_ppo_train_pop``, include/cattleherd.h) instead of o
 
 The members are ``PPOUpdate(backend="native")`` objects -- seeds, hyper-parameter variants -- and stay usable on their
 own.  Each keeps its model, Adam state, generator, schedules, stop word and log; the population owns nothing but the
-kernels' argument tables.  Collection is per member as before: one ``DeviceRolloutBuffer`` each.
+kernels' argument tables.  Collection is per member (one ``DeviceRolloutBuffer`` each) or ``PopulationRollout``'s.
+Members with ``log_stats`` get their records from one ``explained_variance_pop`` call and one host read for the
+population.
 """
 import ctypes
 
@@ -83,12 +85,28 @@ class PPOPopulation:
                     mb.idx, mb.stats = perms[-1].data_ptr(), stats[e * nb].data_ptr()
                 _lib.check(_lib.lib().ch_ppo_train_pop(self._pop, members, len(ups), n, first.batch_size, stream))
         steps = first.n_epochs * nb
+        logging = []   # (update, buffer, table) of the members with log_stats
         for u, rb, stats in zip(ups, rbs, tables):
             # what the member's own entry point would have filled: ch_ppo_train_opt's table for a member with
             # options, ch_ppo_train_log's six columns (the same bits) for one with the log alone, none otherwise
             if not u._opts:
                 stats = stats[:, :_lib.CH_PPO_LOG_STATS].contiguous() if u.log_stats else None
-            u._native_finish(stats, rb, nb, steps)
+            u._native_finish(stats, rb, nb, steps, fill_log=False)
+            if u.log_stats:
+                logging.append((u, rb, stats))
+        if logging:
+            # the logging members' records: their explained variances in one set of launches, everything gathered
+            # into one device tensor and read once; each member's part is what its own _fill_log reads
+            from .train_log import explained_variance_pop
+            with torch.cuda.device(self.device):
+                evs = explained_variance_pop([rb.values.view(-1) for _, rb, _ in logging],
+                                             [rb.returns.view(-1) for _, rb, _ in logging])
+                parts = [u._log_gather(stats, evs[k]) for k, (u, _, stats) in enumerate(logging)]
+                host = torch.cat(parts).cpu().numpy()      # the one read
+            at = 0
+            for (u, _, stats), part in zip(logging, parts):
+                u._log_record(host[at:at + part.numel()], stats.shape, nb)
+                at += part.numel()
         return [steps] * len(ups)
 
     def close(self):

@@ -46,6 +46,10 @@ def _bind():
     lib.ch_rollout_pop_create.argtypes = [i32, i32, ctypes.POINTER(vp)]
     lib.ch_rollout_pop_destroy.argtypes = [vp]
     lib.ch_rollout_collect_pop.argtypes = [vp, vp, ctypes.POINTER(ChRolloutMember), i32, ctypes.POINTER(ChRolloutIO), i32, vp]
+    if hasattr(lib, "ch_rollout_collect_pop_log"):   # (an older library, e.g. an A/B baseline, lacks it)
+        lib.ch_rollout_collect_pop_log.argtypes = [vp, vp, ctypes.POINTER(ChRolloutMember), i32, ctypes.POINTER(ChRolloutIO),
+                                                   i32, ctypes.POINTER(L.ChEpRingPop), vp]
+        lib.ch_rollout_collect_pop_log.restype = ctypes.c_int
     lib.ch__rollout_pop_slice.argtypes = [ctypes.c_int64, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64 * 7)]
     for f in (lib.ch_rollout_pop_create, lib.ch_rollout_pop_destroy, lib.ch_rollout_collect_pop, lib.ch__rollout_pop_slice):
         f.restype = ctypes.c_int
@@ -120,10 +124,13 @@ class PopulationRollout:
         self.terminal_value = torch.zeros((n, 1), **z)
         self._lib, self._pop = None, ctypes.c_void_p()   # the tables: made by the first collect
 
-    def collect(self, actors, critics, log_stds, seeds, bootstrap_truncated=True):
+    def collect(self, actors, critics, log_stds, seeds, bootstrap_truncated=True, ring=None):
         """SB3 collect_rollouts for ``n_steps`` steps of every member on its envs, in one native call on the batch's
         stream.  ``actors`` / ``critics``: one ``DevicePolicy`` per member (one architecture; packed here if they are
-        not), ``log_stds``: one float32 ``[act_dim]`` tensor per member, ``seeds``: one sampling seed per member."""
+        not), ``log_stds``: one float32 ``[act_dim]`` tensor per member, ``seeds``: one sampling seed per member.
+        ``ring``: a ``train_log.PopulationEpisodeRing`` of this batch with one ring per member; every step's ended
+        episodes are appended to their members' rings (ch_rollout_collect_pop_log: one small launch more per step
+        whatever P is; the buffers and the env state do not depend on it).  The ring is not begun here."""
         b, P = self.batch, self.n_members
         actors, critics, log_stds, seeds = list(actors), list(critics), list(log_stds), list(seeds)
         for name, v in (("actors", actors), ("critics", critics), ("log_stds", log_stds), ("seeds", seeds)):
@@ -131,6 +138,11 @@ class PopulationRollout:
                 raise ValueError(f"collect takes one of {name} per member ({P}), got {len(v)}")
         if any(c is None for c in critics) or any(a is None for a in actors):
             raise ValueError("every member needs an actor and a critic (a fused actor-critic is not supported here)")
+        if ring is not None:
+            if ring.batch is not b:
+                raise ValueError("the episode ring belongs to another batch")
+            if ring.n_members != P:
+                raise ValueError(f"the episode ring holds {ring.n_members} members, the population {P}")
         if not self._pop:
             self._lib = _bind()
             L.check(self._lib.ch_rollout_pop_create(P, b.device.index or 0, ctypes.byref(self._pop)))
@@ -151,8 +163,15 @@ class PopulationRollout:
         b._io.terminal_obs = b.terminal_obs.data_ptr()
         b._io.reset_happened, b._io.episode_stats = b.reset_happened.data_ptr(), b.episode_stats.data_ptr()
         try:
-            L.check(self._lib.ch_rollout_collect_pop(b.handle, self._pop, members, P, ctypes.byref(io),
-                                                     int(bool(bootstrap_truncated)), b._stream()), b.handle)
+            if ring is None:
+                L.check(self._lib.ch_rollout_collect_pop(b.handle, self._pop, members, P, ctypes.byref(io),
+                                                         int(bool(bootstrap_truncated)), b._stream()), b.handle)
+            else:
+                if not hasattr(self._lib, "ch_rollout_collect_pop_log"):
+                    raise ImportError("this libcattleherd.so has no ch_rollout_collect_pop_log (an older library?)")
+                L.check(self._lib.ch_rollout_collect_pop_log(b.handle, self._pop, members, P, ctypes.byref(io),
+                                                             int(bool(bootstrap_truncated)), ctypes.byref(ring._ring),
+                                                             b._stream()), b.handle)
         finally:
             b._io.terminal_obs, b._io.reset_happened, b._io.episode_stats = keep
         self._keep = (log_stds, actors, critics)   # alive until the queued launches have read them

@@ -13,6 +13,11 @@ Semantics restated from SB3 2.x; SB3 is not installed here, so the restatement i
 One difference is deliberate: SB3's ``explained_variance`` is float32 numpy, here the float32 inputs are widened
 exactly and every sum is float64 (two passes: the means, then the squared deviations).  CTDE batches only.
 
+A population (``PopulationRollout`` / ``PPOPopulation``) is watched member by member: ``PopulationEpisodeRing`` holds
+one ring per member, filled by one launch per step inside ``PopulationRollout.collect(..., ring=ring)``, each row bit
+for bit the member's solo ``EpisodeRing``; ``fitness()`` is the ``[P, 4]`` table (count, mean return, mean length,
+total) reduced on the device, and ``explained_variance_pop`` the P explained variances in one set of launches.
+
 The DTDE (MARL) driver is watched through RLlib's result dict instead: ``MarlEpisodeRing`` is the env runners' window
 of the last ``metrics_num_episodes_for_smoothing`` episodes with per-agent returns, and their sampling counters, as
 device arrays (``ch_marl_ep_ring``; inside the native collection with ``DeviceMarlRolloutBuffer.collect(...,
@@ -90,6 +95,128 @@ class EpisodeRing:
     def summary(self):
         """``rollout/ep_rew_mean`` and ``rollout/ep_len_mean`` of the ring's content (``summary_of``)."""
         return summary_of(self.entries())
+
+
+def _pop_lib():
+    lib = L.lib()
+    if not hasattr(lib, "ch_ep_ring_pop_record"):
+        raise ImportError("this libcattleherd.so has no ch_ep_ring_pop_record (an older library?)")
+    return lib
+
+
+class PopulationEpisodeRing:
+    """One ``ep_info_buffer`` per member of a population that collects on one CTDE ``HerdBatch``
+    (``PopulationRollout``; member ``p`` owns envs ``[pE, (p + 1)E)``) as device arrays (``ch_ep_ring_pop``):
+    ``ep_return`` float64 [P, W], ``ep_length`` / ``ep_env`` int32 [P, W] (``ep_env``: the member-local env index),
+    ``total`` int64 [P].  Row ``p`` is bit for bit the solo ``EpisodeRing`` of a batch of the member's envs.  The four
+    are views of one device buffer, so ``entries_all()`` is one copy for the whole population; ``fitness()`` reduces
+    the rings on the device."""
+
+    def __init__(self, batch, n_members, window=100):
+        if batch.mode != L.CH_MODE_CTDE:
+            raise ValueError("the episode ring is for CTDE batches")
+        self.batch, self.n_members, self.window = batch, int(n_members), int(window)
+        if self.window < 1:
+            raise ValueError("window must be >= 1")
+        if self.n_members < 1 or batch.n_envs % self.n_members:
+            raise ValueError(f"the batch's {batch.n_envs} envs do not divide evenly among {n_members} members")
+        self.member_envs = batch.n_envs // self.n_members
+        torch = batch.torch
+        P, W = self.n_members, self.window
+        # the 8-byte arrays first: every view is aligned
+        self._cut = (8 * P * W, 8 * P * W + 8 * P, 12 * P * W + 8 * P, 16 * P * W + 8 * P)
+        c = self._cut
+        self._buf = torch.zeros(c[3], dtype=torch.uint8, device=batch.device)
+        self.ep_return = self._buf[:c[0]].view(torch.float64).view(P, W)
+        self.total = self._buf[c[0]:c[1]].view(torch.int64)
+        self.ep_length = self._buf[c[1]:c[2]].view(torch.int32).view(P, W)
+        self.ep_env = self._buf[c[2]:].view(torch.int32).view(P, W)
+        ring = L.ChEpRingPop()
+        ring.window, ring.n_members = W, P
+        for k in ("ep_return", "ep_length", "ep_env", "total"):
+            setattr(ring, k, getattr(self, k).data_ptr())
+        self._ring = ring
+        self._lib = _pop_lib()
+
+    def begin(self):
+        """Empty every member's ring (ch_ep_ring_pop_begin: ``total[p] = 0``)."""
+        b = self.batch
+        L.check(self._lib.ch_ep_ring_pop_begin(b.handle, ctypes.byref(self._ring), b._stream()), b.handle)
+        return self
+
+    def record(self, io=None):
+        """Append the episodes that ended in the step that just ran to their members' rings, one launch for the
+        population (ch_ep_ring_pop_record on the batch's step outputs, or on another ``ChStepIO``)."""
+        b = self.batch
+        L.check(self._lib.ch_ep_ring_pop_record(b.handle, ctypes.byref(self._ring),
+                                                b._io_ref if io is None else ctypes.byref(io), b._stream()), b.handle)
+
+    def _host(self):
+        c, P, W = self._cut, self.n_members, self.window
+        raw = self._buf.cpu().numpy()   # the one copy
+        return (raw[:c[0]].view(np.float64).reshape(P, W), raw[c[1]:c[2]].view(np.int32).reshape(P, W),
+                raw[c[2]:].view(np.int32).reshape(P, W), raw[c[0]:c[1]].view(np.int64))
+
+    def entries_all(self):
+        """Every member's deque content, oldest to newest: a list of P lists of ``(r, l, env)`` (``env`` member-local).
+        One device-to-host copy for the whole population (synchronises)."""
+        W = self.window
+        ret, length, env, total = self._host()
+        return [[(ret[p, k % W], int(length[p, k % W]), int(env[p, k % W]))
+                 for k in range(max(0, int(total[p]) - W), int(total[p]))] for p in range(self.n_members)]
+
+    def entries(self, p):
+        """Member ``p``'s deque content (``entries_all()[p]``)."""
+        return self.entries_all()[p]
+
+    def count(self):
+        """Episodes appended per member since ``begin``: a list of P ints (one small copy; synchronises)."""
+        return [int(v) for v in self.total.cpu().numpy()]
+
+    def summary(self, p):
+        """Member ``p``'s ``rollout/ep_rew_mean`` and ``rollout/ep_len_mean`` (``summary_of(entries(p))``): what a solo
+        ``EpisodeRing`` of the member's envs reports."""
+        return summary_of(self.entries(p))
+
+    def fitness(self, out=None):
+        """The population's fitness table, reduced on the device (ch_ep_ring_pop_summary): a float64 device tensor
+        ``[P, 4]`` of ``(count, mean return, mean length, total)`` per member on the batch's stream, no host
+        synchronisation.  The means are NaN for an empty ring; the returns are not rounded to 6 decimals as
+        ``summary`` rounds them."""
+        b = self.batch
+        torch = b.torch
+        if out is None:
+            out = torch.empty((self.n_members, L.CH_EP_RING_POP_SUMMARY), dtype=torch.float64, device=b.device)
+        L.check(self._lib.ch_ep_ring_pop_summary(ctypes.byref(self._ring), out.data_ptr(), b._stream()))
+        return out
+
+
+def explained_variance_pop(values_list, returns_list, out=None):
+    """``explained_variance`` for P members in one set of launches (ch_explained_variance_pop): returns a float64
+    device tensor ``[P, 2]`` whose row ``p`` is bit for bit ``explained_variance(values_list[p], returns_list[p])``,
+    on the current stream, no host synchronisation.  The tensors: contiguous float32 on one CUDA device, all of one
+    size (separate allocations are fine: the kernels take tables of pointers)."""
+    import torch
+    values_list, returns_list = list(values_list), list(returns_list)
+    P = len(values_list)
+    if P < 1 or len(returns_list) != P:
+        raise ValueError("explained_variance_pop: one values and one returns tensor per member, at least one member")
+    dev, n = values_list[0].device, values_list[0].numel()
+    for t in values_list + returns_list:
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous() or t.numel() != n or n < 1:
+            raise ValueError("explained_variance_pop: contiguous float32 tensors of one size >= 1 on one CUDA device")
+    lib = _pop_lib()
+    if out is None:
+        out = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    scratch = torch.empty(lib.ch_explained_variance_pop_scratch(n, P), dtype=torch.float64, device=dev)
+    # the pointer tables: one upload, values then returns; the copy is queued on the current stream before the launches
+    table = torch.tensor([t.data_ptr() for t in values_list + returns_list], dtype=torch.int64).to(dev, non_blocking=False)
+    with torch.cuda.device(dev):
+        L.check(lib.ch_explained_variance_pop(table[:P].data_ptr(), table[P:].data_ptr(), P, n, out.data_ptr(),
+                                              scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    # the table and the scratch go back to the caching allocator of the stream the launches are queued on: a later
+    # allocation on it reuses them only behind those launches
+    return out
 
 
 def explained_variance(values, returns, out=None):

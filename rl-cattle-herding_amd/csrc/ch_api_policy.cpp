@@ -1,6 +1,6 @@
 // ch_api_policy.cpp — the policy half of the C ABI (see include/cattleherd.h): MLP packing and forwards on device
 // buffers (ch_policy.hip), the on-device PPO rollout buffer and its collection loop, the population's collection
-// (ch_rollout_collect_pop), the per-agent MARL rollout (ch_aux.hip).  It reaches the env through ch_step and step_actor (ch_api.cpp) and a few fields of the handle.
+// (ch_rollout_collect_pop, ch_rollout_collect_pop_log), the per-agent MARL rollout (ch_aux.hip).  It reaches the env through ch_step and step_actor (ch_api.cpp) and a few fields of the handle.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -595,8 +595,13 @@ int ch__rollout_pop_slice(int64_t n_envs, int32_t n_members, int32_t p, int32_t 
     return CH_OK;
 }
 
-int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
-                           const ch_rollout_io* io, int32_t bootstrap_truncated, void* stream) {
+}  // extern "C"
+
+// ch_rollout_collect_pop and ch_rollout_collect_pop_log (`ring`: NULL, or the members' episode rings each step's ended
+// episodes go to)
+static int rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
+                               const ch_rollout_io* io, int32_t bootstrap_truncated, const ch_ep_ring_pop* ring,
+                               void* stream) {
     const std::string w = "ch_rollout_collect_pop: ";
     if (!h) return fail(nullptr, CH_ERR_INVALID, w + "NULL handle");
     if (!pop || !members || !io || !io->step) return fail(h, CH_ERR_INVALID, w + "NULL argument");
@@ -610,6 +615,13 @@ int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_m
         !sio->terminal_obs || !sio->reset_happened || (bootstrap_truncated && !io->terminal_value))
         return fail(h, CH_ERR_INVALID, w + "NULL argument: mean, value, env_actions, the step buffers (obs, reward, terminated, "
                                            "truncated, terminal_obs, reset_happened) and terminal_value are required");
+    EpRingArgs er;   // the recorder's arguments: the rings and this io's reset_happened / episode_stats
+    if (ring) {
+        if (int rc = ep_ring_pop_args(h, ring, sio, er, "ch_rollout_collect_pop_log", true)) return rc;
+        if (ring->n_members != n_members)
+            return fail(h, CH_ERR_INVALID, "ch_rollout_collect_pop_log: the ring's n_members (" + std::to_string(ring->n_members) +
+                                               ") is not the call's (" + std::to_string(n_members) + ")");
+    }
     const int P = n_members;
     const int64_t E = h->E / P;
     const ch_rollout_member& m0 = members[0];
@@ -752,6 +764,10 @@ int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_m
         HIP_TRY(h, launch_mlp_pop(plan[kRoPopStep], dev[kRoPopStep], P, t, st));
         if (bootstrap_truncated && t > 0 && t % kTvEvery == 0) HIP_TRY(h, flush());
         if (int rc = ch_step(h, &s, stream)) return rc;
+        // the episode rings, where ch_rollout_collect_log records: step t's reset_happened / episode_stats are the
+        // launch above's, and nothing before step t + 1's env step writes them (the forwards, the flush and the post
+        // write the members' buffers, the queue and the scratch outputs only)
+        if (ring) HIP_TRY(h, launch_ep_ring_record_pop(er, P, st));
     }
     // the tail, as the solo epilogue path: the last step's post, the last flush, V(obs after the last step), GAE
     HIP_TRY(h, launch_rollout_pop(dev[kRoPopStep], P, E, 0, T, st));
@@ -759,6 +775,19 @@ int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_m
     HIP_TRY(h, launch_mlp_pop(plan[kRoPopLast], dev[kRoPopLast], P, 0, st));
     HIP_TRY(h, launch_rollout_pop(dev[kRoPopStep], P, E, 2, T, st));
     return CH_OK;
+}
+
+extern "C" {
+
+int ch_rollout_collect_pop(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
+                           const ch_rollout_io* io, int32_t bootstrap_truncated, void* stream) {
+    return rollout_collect_pop(h, pop, members, n_members, io, bootstrap_truncated, nullptr, stream);
+}
+
+int ch_rollout_collect_pop_log(ch_handle* h, ch_rollout_pop* pop, const ch_rollout_member* members, int32_t n_members,
+                               const ch_rollout_io* io, int32_t bootstrap_truncated, const ch_ep_ring_pop* ring,
+                               void* stream) {
+    return rollout_collect_pop(h, pop, members, n_members, io, bootstrap_truncated, ring, stream);
 }
 
 }  // extern "C"

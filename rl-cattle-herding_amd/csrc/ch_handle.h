@@ -125,6 +125,12 @@ int device_status(ch_handle* h, int word);
 // ring, a CTDE handle, and -- with `io` -- a step io that carries reset_happened and episode_stats; fills `a`
 int ep_ring_args(ch_handle* h, const ch_ep_ring* ring, const ch_step_io* io, ch::EpRingArgs& a, const char* who);
 
+// a population's rings' checks (ch_api_train_log.cpp; ch_ep_ring_pop_* and ch_rollout_collect_pop_log share them): whole
+// rings with window >= 1 and n_members >= 1, and -- `h_needed` -- a CTDE handle whose envs divide among the members and,
+// with `io`, a step io that carries reset_happened and episode_stats; fills `a` for launch_ep_ring_record_pop
+int ep_ring_pop_args(ch_handle* h, const ch_ep_ring_pop* ring, const ch_step_io* io, ch::EpRingArgs& a, const char* who,
+                     bool h_needed);
+
 // the MARL episode ring's checks (ch_api_train_log.cpp; ch_marl_ep_ring_record and ch_marl_rollout_collect_log
 // share them): a whole ring, a MARL handle under the wrapper's semantics, and -- with `io` -- a step io that carries
 // reward and reset_happened; fills `a` but for `live`

@@ -274,6 +274,15 @@ hipError_t launch_ep_ring_record(const EpRingArgs& a, hipStream_t st);
 long long ev_scratch_doubles(long long n);   // n >= 1
 hipError_t launch_explained_variance(const float* values, const float* returns, long long n, double* out, double* scratch,
                                      hipStream_t st);
+// The population's (ch_ep_ring_pop_*, ch_explained_variance_pop).  `a` describes all `members` rings at
+// once: E the envs of ONE member, reset / stats the whole handle's [members * E] rows, ep_return / ep_length / ep_env
+// the first row of [members][W], total [members]; workgroup p takes its slice (grid (members), one launch).
+hipError_t launch_ep_ring_record_pop(const EpRingArgs& a, int members, hipStream_t st);
+// out [members][4]: count, mean return, mean length, total (reads W, ep_return, ep_length, total of `a`)
+hipError_t launch_ep_ring_pop_summary(const EpRingArgs& a, int members, double* out, hipStream_t st);
+// values / returns: device tables of `members` device pointers; out [members][2]; scratch [members][ev_scratch_doubles(n)]
+hipError_t launch_explained_variance_pop(const float* const* values, const float* const* returns, int members, long long n,
+                                         double* out, double* scratch, hipStream_t st);
 
 // ch_marl_ep_ring.hip: the RLlib training log's episode ring for MARL handles (ch_marl_ep_ring_*): the ring, the open
 // episodes' accumulators, the sampling counters, and the outputs of the step the recorder follows
